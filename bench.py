@@ -11,13 +11,22 @@ bitwise those of K single dr_step launches, tests/test_rollout_gpu.py); the
 launches are captured in one hipGraph and replayed, bracketed by barrier +
 synchronize on both sides; the max over ranks is taken.  `--headline step`
 times one dr_step launch per step instead (the kernel PPO's rollout uses;
-always reported as `single_step`).
+reported as `single_step` by every `--full` run).
 
 Multi-GPU: one process per GPU, independent env shards (global env ids
 rank*N+i), no data-path collective -> "scaling": "weak".  Two launch forms:
 under torchrun (WORLD_SIZE set; it must equal --gpus), or directly as
 `python bench.py --gpus N`, where this process starts the N ranks itself
 (spawn_ranks; it never touches the GPU) and rank 0 prints the line.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps of the headline and prints the line with the headline's
+own roofline block; `--dump-outputs DIR` also writes the last timed step's
+obs / reward / done and the env state after it as DIR/<name>.npy (the same
+arguments give the same inputs, so two builds compare output for output).
+Every other leg below (single_step, host_floor_us, cpu_baseline, the
+companions, ppo, rollout_kernel, --extra) runs with `--full` only; the
+options that shape those legs have no effect without it.
 
 The JSON line also carries
   roofline      the headline kernel: algorithmic bytes per launch (per env-
@@ -202,7 +211,17 @@ def parse():
                          "dr_step launch per step")
     ap.add_argument("--headline-k", type=int, default=32,
                     help="max steps per rollout-kernel launch in the headline")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baseline, single_step, "
+                         "host floor, companions, rollout_kernel, ppo, --extra); without it "
+                         "the options of those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's obs / reward / "
+                         "done and the env state after it as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.extra and not args.full:
+        ap.error("--extra is a leg of --full: pass --full --extra")
+    return args
 
 
 # Start alignment at world > 1: after the barrier and the device
@@ -347,19 +366,84 @@ def cpu_baseline(seconds):
             "plan": plan}
 
 
-def time_env(args, dtype_name, n_envs, rank, world, device, steps, warmup, variant="gym"):
+# the pre-generated actions kept in HBM: one draw per step up to this many
+# bytes (16,384 steps at 65,536 envs; the 4,194,304-env legs' 220 steps fit)
+ACTION_BYTES_MAX = 16 << 30
+# --dump-outputs writes at most this many bytes in all
+DUMP_BYTES_MAX = 64 << 20
+# the last timed step's outputs and the state after it (--dump-outputs)
+HEADLINE_OUTPUTS = {}
+
+
+def resident_actions(n_envs, total, kmax, rank, device):
+    """The actions of steps 0 .. total-1, generated before the timed region
+    and resident in HBM: step t draws random_actions(seed 7, step t).  A run
+    whose draws would exceed ACTION_BYTES_MAX keeps the first `period` of them
+    and reads them round (step t uses draw t % period; the first kmax - 1
+    draws are repeated behind the last, so that any launch's steps stay one
+    contiguous slice).  Returns at(t, k): the (k, n_envs, 4) actions of steps
+    t .. t+k-1, k <= kmax."""
     import torch
 
-    from drone_rl_amd import DroneBatch, random_actions
+    from drone_rl_amd import random_actions
+    period = max(kmax, ACTION_BYTES_MAX // (n_envs * 16))
+    rows = total if total <= period else period + kmax - 1
+    acts = torch.empty(rows, n_envs, 4, dtype=torch.float32, device=device)
+    for j in range(rows):
+        random_actions(n_envs, seed=7, step=j if total <= period else j % period,
+                       env_id_offset=rank * n_envs, out=acts[j])
+
+    def at(t, k=1):
+        s = t if total <= period else t % period
+        return acts[s:s + k]
+    return at
+
+
+def keep_outputs(b, obs, rew, done):
+    """HEADLINE_OUTPUTS: copies of the last timed step's obs / reward / done
+    and of the env state after it (called after the timer)."""
+    HEADLINE_OUTPUTS.clear()
+    HEADLINE_OUTPUTS.update({"obs": obs.clone(), "reward": rew.clone(), "done": done.clone()})
+    for f in ("pos", "vel", "euler", "omega"):
+        HEADLINE_OUTPUTS["state_" + f] = b.get(f).clone()
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array as dirname/<name>.npy, float64 where it is float64
+    and float32 otherwise (done 0 / 1).  All arrays have one row per env;
+    where they would exceed DUMP_BYTES_MAX in all, the rows of a fixed,
+    seeded sample of the envs are written, with the sampled env numbers as
+    env_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    n = len(next(iter(host.values())))
+    per_env = sum(a.nbytes // n for a in host.values()) + 8
+    if n * per_env > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // per_env,
+                                                      replace=False))
+        host = {name: a[idx] for name, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
+def time_env(args, dtype_name, n_envs, rank, world, device, steps, warmup, variant="gym",
+             keep=False):
+    import torch
+
+    from drone_rl_amd import DroneBatch
     dtype = torch.float64 if dtype_name == "f64" else torch.float32
     b = DroneBatch(n_envs, variant, dtype=dtype, device=device, seed=2025,
                    env_id_offset=rank * n_envs, auto_reset=True)
     b.reset()
     total = warmup + steps
     # inputs resident in HBM before the timed region
-    acts = torch.empty(total, n_envs, 4, dtype=torch.float32, device=device)
-    for t in range(total):
-        random_actions(n_envs, seed=7, step=t, env_id_offset=rank * n_envs, out=acts[t])
+    at = resident_actions(n_envs, total, 1, rank, device)
+    acts = [at(t)[0] for t in range(total)]
     for t in range(warmup):
         b.step(acts[t])
     stream = torch.cuda.current_stream(device)
@@ -397,6 +481,8 @@ def time_env(args, dtype_name, n_envs, rank, world, device, steps, warmup, varia
     elapsed, gpu_ms = tm["wall_s"], tm["gpu_ms"]
     # sanity: the env is alive (episodes end and reset under a random policy)
     ep = b.get("ep_num").float().mean().item()
+    if keep:
+        keep_outputs(b, b.obs, b.rew, b.done)    # step() writes the batch's own buffers
     b.close()
     del graph
     return elapsed, gpu_ms, ep
@@ -413,16 +499,14 @@ def time_headline(args, n_envs, rank, world, device, steps, warmup, kmax):
     Returns (wall seconds, GPU ms over the timed launches, launches, mean ep_num)."""
     import torch
 
-    from drone_rl_amd import DroneBatch, random_actions
+    from drone_rl_amd import DroneBatch
     dtype = torch.float64 if args.state_dtype == "f64" else torch.float32
     b = DroneBatch(n_envs, "gym", dtype=dtype, device=device, seed=2025,
                    env_id_offset=rank * n_envs, auto_reset=True)
     b.reset()
     total = warmup + steps
-    acts = torch.empty(total, n_envs, 4, dtype=torch.float32, device=device)
-    for t in range(total):
-        random_actions(n_envs, seed=7, step=t, env_id_offset=rank * n_envs, out=acts[t])
     k0 = min(kmax, max(steps, warmup, 1))
+    acts = resident_actions(n_envs, total, k0, rank, device)
     obs = torch.empty(k0, n_envs, b.obs_dim, device=device)
     rew = torch.empty(k0, n_envs, device=device)
     done = torch.empty(k0, n_envs, dtype=torch.uint8, device=device)
@@ -431,7 +515,7 @@ def time_headline(args, n_envs, rank, world, device, steps, warmup, kmax):
         n = 0
         while t0 < t1:
             k = min(k0, t1 - t0)
-            b.rollout(k, acts[t0:t0 + k], obs_out=obs[:k], rew_out=rew[:k], done_out=done[:k])
+            b.rollout(k, acts(t0, k), obs_out=obs[:k], rew_out=rew[:k], done_out=done[:k])
             t0 += k
             n += 1
         return n
@@ -460,7 +544,7 @@ def time_headline(args, n_envs, rank, world, device, steps, warmup, kmax):
         t = warmup
         while t < total:
             k = min(k0, total - t)
-            calls.append((b.handle, k, acts[t].data_ptr(), obs.data_ptr(), rew.data_ptr(),
+            calls.append((b.handle, k, acts(t, k).data_ptr(), obs.data_ptr(), rew.data_ptr(),
                           done.data_ptr(), stream.cuda_stream))
             t += k
         fn = b.L.dr_rollout
@@ -546,6 +630,9 @@ def time_headline(args, n_envs, rank, world, device, steps, warmup, kmax):
                               "start_alignment": "common CLOCK_MONOTONIC deadline agreed "
                                                  "before t0 (bench.start_deadline)"})
     ep =b.get("ep_num").float().mean().item()
+    if args.dump_outputs:
+        last = steps - (launches - 1) * k0 - 1      # the last launch's last step
+        keep_outputs(b, obs[last], rew[last], done[last])
     b.close()
     graphed = g is not None
     del g
@@ -1078,7 +1165,7 @@ def main():
         sys.exit(2)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)      # before any GPU work
 
     import torch
@@ -1127,8 +1214,12 @@ def main():
                              "kernel": "env_step_kernel", "bytes_per_env_step": bpe,
                              "avg_launch_us": round(pl * 1e6, 3)}}
 
-    el_s, gm_s, ep_s = time_env(args, args.state_dtype, N, rank, world, device, K, args.warmup)
-    single = step_block(el_s, gm_s, K, N)
+    single = None
+    if args.full or args.headline == "step":
+        el_s, gm_s, ep_s = time_env(args, args.state_dtype, N, rank, world, device, K,
+                                    args.warmup,
+                                    keep=bool(args.dump_outputs) and args.headline == "step")
+        single = step_block(el_s, gm_s, K, N)
     if args.headline == "rollout":
         elapsed, gpu_ms, launches, ep, packet_ms, graphed = time_headline(
             args, N, rank, world, device, K, args.warmup, args.headline_k)
@@ -1184,7 +1275,10 @@ def main():
         elapsed, gpu_ms, ep = el_s, gm_s, ep_s
         roof = single["roofline"]
         graphed = not args.no_graph
-    if args.headline == "rollout" and world == 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, HEADLINE_OUTPUTS)
+    HEADLINE_OUTPUTS.clear()
+    if args.full and args.headline == "rollout" and world == 1:
         # what one direct launch + synchronize costs on the host side (the
         # driver's --steps 20 is one launch): a near-empty launch on the same
         # path, wall against its dispatch packet
@@ -1222,12 +1316,12 @@ def main():
                               else "dr_step (one launch per step)"),
                    "parallelism": f"dp{world} (independent env shards)"},
         "roofline": roof,
-        "single_step": single,
+        **({"single_step": single} if single is not None else {}),
         "mean_ep_num": round(ep, 2),
     }
     if HEADLINE_NODE:
         out["node_timing"] = dict(HEADLINE_NODE)
-    if world == 1 and not args.no_companion:
+    if args.full and world == 1 and not args.no_companion:
         # cache-busting companion of the headline: the same
         # kernel at 4,194,304 envs, where the step is HBM-bound, not launch-
         # and latency-bound as at 65,536 (not the bench value)
@@ -1259,7 +1353,7 @@ def main():
             "roofline": {"bound": "hbm", "achieved": round(achr, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achr / HBM_PEAK_GBS, 4), "traffic": trr,
                          "traffic_GBs": round(trr / plr / 1e9, 1) if trr else None}}
-    if world == 1 and args.rollout_k > 0:
+    if args.full and world == 1 and args.rollout_k > 0:
         # SURVEY 7 "hard parts" (a): the K-step random-policy rollout kernel,
         # same envs and action stream, every step's obs / rew / done written
         # (bitwise the K single steps; tests/test_rollout_gpu.py)
@@ -1289,9 +1383,9 @@ def main():
     if cpu is not None:
         out["cpu_baseline"] = cpu
     out["kernel_source_hash"] = kernel_source_hash()[:12]
-    if args.ppo_updates > 0:
+    if args.full and args.ppo_updates > 0:
         out["ppo"] = time_ppo(args, rank, world, device)
-    if args.extra and world == 1:
+    if args.full and args.extra and world == 1:
         ex = {}
         # the data-parallel optimizer step (PPOTrainer at world > 1: deferred
         # finish -> gradient all-reduce -> clip+Adam) timed on one GPU: with

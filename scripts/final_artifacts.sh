@@ -29,7 +29,7 @@ prof)
   step smoke 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
   rm -rf "$PWD/$OUT/ks"
   step kstats 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/ks" -o run \
-      -- python3 "$PWD/bench.py" --steps 640 --warmup 64 --ppo-updates 2 --no-cpu-baseline
+      -- python3 "$PWD/bench.py" --full --steps 640 --warmup 64 --ppo-updates 2 --no-cpu-baseline
   step gridstats 60 python3 scripts/kernel_grid_stats.py "$OUT/ks/run_kernel_trace.csv" \
       "$OUT/rollout_grid_stats.json" env_rollout
   rm -f "$OUT"/ks/*kernel_trace.csv
@@ -45,7 +45,7 @@ pmc)
 bench)
   for b in default:"" steps20_a:"--steps 20 --warmup 5" steps20_b:"--steps 20 --warmup 5" \
            extra:"--no-cpu-baseline --extra"; do
-    step bench_${b%%:*} 400 python bench.py ${b#*:}
+    step bench_${b%%:*} 400 python bench.py --full ${b#*:}
     grep '^{' $OUT/bench_${b%%:*}.log | tail -1 > $OUT/bench_${b%%:*}.json
   done
   ;;

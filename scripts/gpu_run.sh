@@ -23,12 +23,12 @@ if [[ $WHAT == all || $WHAT == test ]]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [[ $WHAT == all || $WHAT == bench ]]; then
-  step bench 600 python bench.py --extra
+  step bench 600 python bench.py --full --extra
   cat $OUT/bench.log | grep '^{' > $OUT/bench.json || true
 fi
 if [[ $WHAT == all || $WHAT == prof ]]; then
   export TMPDIR=/tmp
   step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$PWD/$OUT/prof" -o run -- python3 "$PWD/bench.py" --no-cpu-baseline --no-companion
+      -d "$PWD/$OUT/prof" -o run -- python3 "$PWD/bench.py" --full --no-cpu-baseline --no-companion
 fi
 echo "== done"

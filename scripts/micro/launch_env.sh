@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 timeout -k 10 200 python scripts/micro/streams.py > gpurun_out/streams.log 2>&1 || exit $?
 grep 'S=' gpurun_out/streams.log
 for v in 1 0 1 0; do
-  HIP_FORCE_DEV_KERNARG=$v timeout -k 10 120 python bench.py --no-cpu-baseline --ppo-updates 0 \
+  HIP_FORCE_DEV_KERNARG=$v timeout -k 10 120 python bench.py --full --no-cpu-baseline --ppo-updates 0 \
     --steps 2000 > gpurun_out/karg_$v.log 2>&1 || exit $?
   echo "DEV_KERNARG=$v $(grep -o '"avg_launch_us": [0-9.]*' gpurun_out/karg_$v.log) $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/karg_$v.log)"
 done

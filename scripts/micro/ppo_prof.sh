@@ -9,7 +9,7 @@ i=0
 for lib in "${libs[@]}"; do
   i=$((i+1)); D=$PWD/gpurun_out/pprof$i; rm -rf $D
   DRONERL_LIB=$(realpath $lib) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o run \
-    -- python3 $PWD/bench.py --no-cpu-baseline --no-companion --steps 50 --warmup 10 --ppo-updates 3 > $D.log 2>&1 || exit $?
+    -- python3 $PWD/bench.py --full --no-cpu-baseline --no-companion --steps 50 --warmup 10 --ppo-updates 3 > $D.log 2>&1 || exit $?
   rm -f $D/*kernel_trace.csv
   echo "== $lib: $(grep -o '"updates_per_s": [0-9.]*' $D.log)"
   python3 - "$D/run_kernel_stats.csv" <<'PY'

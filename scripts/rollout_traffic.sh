@@ -15,7 +15,7 @@ for k in 32 20; do
   if [ $k = 32 ]; then ARGS="--steps 960 --warmup 64"; else ARGS="--steps 20 --warmup 20"; fi
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $c --output-format csv -d "$OUT/k${k}_$c" -o run \
-        -- python3 "$PWD/bench.py" --no-cpu-baseline --no-companion --no-graph --ppo-updates 0 \
+        -- python3 "$PWD/bench.py" --full --no-cpu-baseline --no-companion --no-graph --ppo-updates 0 \
         --rollout-k 0 $ARGS > "$OUT/k${k}_$c.log" 2>&1
     rc=$?; echo "k=$k $c rc=$rc"
     if [ $rc -ne 0 ]; then tail -5 "$OUT/k${k}_$c.log"; exit $rc; fi
@@ -23,7 +23,7 @@ for k in 32 20; do
 done
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d "$OUT/c4m_$c" -o run \
-      -- python3 "$PWD/bench.py" --no-cpu-baseline --no-graph --ppo-updates 0 --rollout-k 0 \
+      -- python3 "$PWD/bench.py" --full --no-cpu-baseline --no-graph --ppo-updates 0 --rollout-k 0 \
       --steps 20 --warmup 5 > "$OUT/c4m_$c.log" 2>&1
   rc=$?; echo "companion $c rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/c4m_$c.log"; exit $rc; fi

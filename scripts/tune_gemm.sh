@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 OUT=gpurun_out/tune
 mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --steps 20 --warmup 5 --ppo-updates 3"
+B="python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --ppo-updates 3"
 timeout -k 10 300 $B > $OUT/base.log 2>&1 || exit $?
 PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_VERBOSE=1 \
 PYTORCH_TUNABLEOP_FILENAME=$OUT/tunableop.csv \

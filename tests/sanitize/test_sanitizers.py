@@ -30,7 +30,10 @@ def _build(what, target, sources):
 
 
 def _run(preload, extra_env, tests):
-    env = dict(os.environ, LD_PRELOAD=preload,
+    # host code only: the child sees no GPU agent (loading the HIP library
+    # would otherwise initialise the runtime's device pools under the
+    # sanitizer's allocator, which a host sanitizer run cannot serve)
+    env = dict(os.environ, ROCR_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:detect_odr_violation=0",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", **extra_env)
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",

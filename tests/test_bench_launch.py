@@ -44,7 +44,7 @@ def test_direct_gpus2_starts_two_ranks():
     """The driver's BENCH form with --gpus 2, on the one-GPU box: both ranks
     share the card over gloo (RCCL refuses two ranks per device)."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--ppo-updates", "1", "--no-companion", "--rollout-k", "0"],
+                        "--full", "--ppo-updates", "1", "--no-companion", "--rollout-k", "0"],
                        env=_env(DRONERL_DIST_BACKEND="gloo"), capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
