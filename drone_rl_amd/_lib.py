@@ -27,6 +27,7 @@ ABI_VERSION = 16                # DR_ABI_VERSION in include/dronerl.h
 DR_VARIANT_GYM = 0
 DR_VARIANT_VECTORIZED = 1
 DR_VARIANT_MOVING = 2
+DR_VARIANT_SMOOTH = 3
 DR_STATE_F64 = 0
 DR_STATE_F32 = 1
 DR_RNG_PHILOX = 0
@@ -34,7 +35,7 @@ DR_RNG_HOST_UNIFORMS = 1
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
-          "ep_length": 9, "motion": 10}
+          "ep_length": 9, "motion": 10, "motor": 11}
 
 
 class dr_config(ctypes.Structure):
@@ -86,6 +87,8 @@ SIGNATURES = {
     "dr_set_state": (c_int, [_P, c_int, _P, _P]),
     "dr_set_reset_uniforms": (c_int, [_P, _P]),
     "dr_set_seed": (c_int, [_P, c_uint64]),
+    "dr_set_smoothing": (c_int, [_P, c_float, c_float]),
+    "dr_get_smoothing": (c_int, [_P, _P, _P]),
     "dr_rollout": (c_int, [_P, c_int32, _P, _P, _P, _P, _P]),
     "dr_rollout_timed": (c_int, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "dr_rollout_random": (c_int, [_P, c_int32, c_uint64, c_int64, c_float, c_float, _P, _P,

@@ -6,7 +6,9 @@
 // load and store of a wave is one contiguous 512 B (f64) or 256 B (f32)
 // transaction.  Actions arrive as (N,4) f32 (one 16 B load per lane).  The
 // (N,15) f32 observation rows (60 B, not 16 B aligned per env) are staged
-// through LDS and leave the block as contiguous float4 stores.
+// through LDS and leave the block as contiguous float4 stores.  The moving
+// variant adds 9 f32 motion arrays and 3 obs floats, the smooth variant 4 f32
+// motor-force arrays and 4 obs floats (DESIGN.md sections 11 and 14).
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -189,7 +191,8 @@ struct EnvView {
     double *eps;
     float *ep_ret;
     int32_t *ep_len;
-    float *mot;       // moving variant: 9 f32 arrays (a xyz, w xyz, ph xyz)
+    float *mot;       // moving variant: 9 f32 arrays (a xyz, w xyz, ph xyz);
+                      // smooth variant: 4 f32 arrays (the motor forces)
     int64_t n;
     int64_t env_id_offset;
     const double *host_u;  // DR_RNG_HOST_UNIFORMS buffer, else nullptr
@@ -422,9 +425,47 @@ __device__ inline void moving_reset_regs(const EnvView<S> &v, int64_t i, int mod
     }
 }
 
+// ---- smooth-control variant (DR_VARIANT_SMOOTH) ----
+// Observation width of a variant.
+template <int VAR>
+constexpr int od_of() {
+    return VAR == DR_VARIANT_GYM ? 15
+                                 : (VAR == DR_VARIANT_MOVING ? 18 : (VAR == DR_VARIANT_SMOOTH ? 19 : 12));
+}
+// What a variant's kernels take beyond the shared arguments: nothing, or the
+// smooth variant's two parameters.  A trailing kernel argument of its own, so
+// the argument blocks of the other variants' kernels stay as they were.
+template <int VAR>
+struct VarArgs {};
+template <>
+struct VarArgs<DR_VARIANT_SMOOTH> {
+    float alpha;   // lag blend dt / (tau + dt), in (0, 1]
+    float lam;     // action-rate penalty, >= 0
+};
+// the force every motor applies after a reset: f32(mass * g / 4)
+constexpr float kHover32 = (float)(kMass * kG / 4);
+
+// The motor lag on registers: f <- (1 - alpha) f + alpha a, every operation
+// one f32 rounding (no FMA: the file is compiled with contraction off).
+// Returns the forces as the action the physics sees and sets dev_sq = |a - f|^2
+// against the forces BEFORE the update.
+__device__ inline float4 smooth_filter(float4 a, float f[4], float alpha, float &dev_sq) {
+    const float c[4] = {a.x, a.y, a.z, a.w};
+    float d[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] = c[j] - f[j];
+    dev_sq = ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3];
+    const float b = 1.0f - alpha;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = b * f[j] + alpha * c[j];
+    return make_float4(f[0], f[1], f[2], f[3]);
+}
+
+// `ext`: the floats past the gym's 15 (moving: the target velocity, 3;
+// smooth: the motor forces, 4).
 template <typename S, int OD>
 __device__ inline void make_obs(const S st[F_N], float ob[OD],
-                                const float *tvel = nullptr) {
+                                const float *ext = nullptr) {
     // _get_obs: f32(concat(pos, vel, euler, omega[, target - pos]))  (79)
 #pragma unroll
     for (int k = 0; k < 12; ++k) ob[k] = (float)st[k];
@@ -434,7 +475,11 @@ __device__ inline void make_obs(const S st[F_N], float ob[OD],
     }
     if constexpr (OD == 18) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) ob[15 + k] = tvel[k];
+        for (int k = 0; k < 3; ++k) ob[15 + k] = ext[k];
+    }
+    if constexpr (OD == 19) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ob[15 + k] = ext[k];
     }
 }
 
@@ -614,9 +659,14 @@ __device__ inline const T *at(const T *base, int64_t i) {
 // before the first global load is issued, not two.
 template <typename S, int VAR, bool MON, int RPW, bool HU, bool NTL>
 __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
-                                                             StepIO io, FieldPtrs<S> fp) {
-    constexpr int OD = VAR == DR_VARIANT_GYM ? 15 : (VAR == DR_VARIANT_MOVING ? 18 : 12);
+                                                             StepIO io, FieldPtrs<S> fp,
+                                                             VarArgs<VAR> va) {
+    constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
+    // the gym's stored target and reset (the smooth variant is the gym env
+    // behind a motor lag)
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH;
+    constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
     // ONE batch of scalar loads: the compiler otherwise issues them in three
@@ -657,7 +707,13 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     for (int k = 0; k < F_EUL; ++k) st[k] = ld_in<NTL>(at(fp.p[k], i));
     S cen[3];
     float mp[9], tvel[3];
-    if constexpr (VAR == DR_VARIANT_GYM) {
+    float fm[4], dev_sq = 0.f;      // smooth: motor forces, |command - force|^2
+    const float *const ext = SMOOTH ? fm : tvel;   // the obs past the gym's 15
+    if constexpr (SMOOTH) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
+    }
+    if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = ld_in<NTL>(at(fp.p[k], i));
     } else if constexpr (VAR == DR_VARIANT_MOVING) {
@@ -695,7 +751,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // latency.
     __builtin_amdgcn_sched_barrier(0);
     u32x4 pre0{};
-    if constexpr (VAR == DR_VARIANT_GYM && DR_HOIST_RESET) {
+    if constexpr (GYMSTATE && DR_HOIST_RESET) {
         if constexpr (!HU) {
             const uint64_t gid = (uint64_t)(v.env_id_offset + i);
             pre0 = philox4x32_10(u32x4{(uint32_t)(ep_old + 1), (uint32_t)gid,
@@ -709,11 +765,22 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     }
 
     bool crash;
-    const S r = physics_step<S, VAR>(st, act, v.dt, crash);
+    S r;
+    if constexpr (SMOOTH) {
+        // the physics sees the lagged forces, not the command
+        r = physics_step<S, VAR>(st, smooth_filter(act, fm, va.alpha, dev_sq), v.dt, crash);
+    } else {
+        r = physics_step<S, VAR>(st, act, v.dt, crash);
+    }
     DR_STAMP(2);
     step += 1;                                             // (155)
     const bool done = live && (crash || (step >= v.max_steps));   // (156-157)
-    const float rf = (float)r;                             // SB3 f32 buffer
+    float rf = (float)r;                                   // SB3 f32 buffer
+    if constexpr (SMOOTH) {
+        // uniform branch: at lam == 0 the reward is the gym's even where
+        // dev_sq overflowed
+        if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
+    }
 #if DR_LOADS_LANDED
     // Every value loaded up front has landed before the first store is
     // issued (they were issued first and the physics took longer than
@@ -732,7 +799,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         st_out(at(io.done, i), (uint8_t)done);
     }
 #if !DR_OBS_ONCE
-    make_obs<S, OD>(st, ob, tvel);
+    make_obs<S, OD>(st, ob, ext);
 #endif
 
     float ret = 0.f;
@@ -746,17 +813,21 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             // DummyVecEnv: keep the terminal obs, reset in the same step.
             if (io.term_obs) {
 #if DR_OBS_ONCE
-                make_obs<S, OD>(st, ob, tvel);
+                make_obs<S, OD>(st, ob, ext);
 #endif
 #pragma unroll
                 for (int k = 0; k < OD; ++k) io.term_obs[i * OD + k] = ob[k];
             }
             step = 0;
-            if constexpr (VAR == DR_VARIANT_GYM) {
+            if constexpr (GYMSTATE) {
                 gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old,
                                DR_HOIST_RESET ? &pre0 : nullptr);
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
+                if constexpr (SMOOTH) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) fm[k] = kHover32;
+                }
             } else {
                 moving_reset_regs(v, i, HU ? 1 : 0, st, cen, mp, ep_old, eps_old);
 #pragma unroll
@@ -766,14 +837,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                 moving_target(cen, mp, 0, (float)v.dt, &st[F_TGT], tvel);
             }
 #if !DR_OBS_ONCE
-            make_obs<S, OD>(st, ob, tvel);
+            make_obs<S, OD>(st, ob, ext);
 #endif
         }
     }
 #if DR_OBS_ONCE
     // ONE observation pass over the post-reset state (the terminal obs is
     // formed inside the reset branch only when the caller keeps it)
-    make_obs<S, OD>(st, ob, tvel);
+    make_obs<S, OD>(st, ob, ext);
 #endif
     if constexpr (MON) {
         if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !crash);
@@ -793,6 +864,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
         for (int k = 0; k < 12; ++k) st_out(at(fp.p[k], i), st[k]);
         st_out(at(p_step, i), step);
+        if constexpr (SMOOTH) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
+        }
     }
     DR_STAMP(4);
     if (!live) {
@@ -842,9 +917,12 @@ struct RolloutIO {
 
 template <typename S, int VAR, int RPW, bool GEN>
 __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, RolloutIO io,
-                                                                FieldPtrs<S> fp) {
-    constexpr int OD = VAR == DR_VARIANT_GYM ? 15 : (VAR == DR_VARIANT_MOVING ? 18 : 12);
+                                                                FieldPtrs<S> fp,
+                                                                VarArgs<VAR> va) {
+    constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH;
+    constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
     const int64_t base = (int64_t)blockIdx.x * (DR_ENV_WPB * RPW);
@@ -860,7 +938,15 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     for (int k = 0; k < F_EUL; ++k) st[k] = *at(fp.p[k], i);
     S cen[3];
     float mp[9], tvel[3];
-    if constexpr (VAR == DR_VARIANT_GYM) {
+    // smooth: the motor forces, carried in registers over the launch, and
+    // this step's |command - force|^2
+    float fm[4], dev_sq = 0.f;
+    const float *const ext = SMOOTH ? fm : tvel;
+    if constexpr (SMOOTH) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
+    }
+    if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
     } else if constexpr (VAR == DR_VARIANT_MOVING) {
@@ -906,6 +992,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     asm volatile("v_mov_b32 %0, %1" : "=v"(max_steps) : "s"(v.max_steps));
     // one step from the action's motor mixes: the body of env_step_kernel
     // on registers
+    // the motor mixes the physics sees for command `act`: the command's own,
+    // or (smooth) those of the lagged forces, which the lag updates here
+    auto mix_of = [&](const float4 act) -> MotorMix {
+        if constexpr (SMOOTH) return motor_mix(smooth_filter(act, fm, va.alpha, dev_sq));
+        else return motor_mix(act);
+    };
     auto step_one = [&](const MotorMix mx, const int t) {
         asm volatile("" : "+s"(vk.seed_lo), "+s"(vk.seed_hi));
         if constexpr (GYMLIKE) {
@@ -926,16 +1018,27 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         const bool done = live && (crash || (step >= max_steps));
         const int64_t row = (int64_t)t * n_;
         if (live) {
-            st_out(at(io.rew + row, i), (float)r);
+            if constexpr (SMOOTH) {
+                float rf = (float)r;
+                // uniform branch, as in env_step_kernel
+                if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
+                st_out(at(io.rew + row, i), rf);
+            } else {
+                st_out(at(io.rew + row, i), (float)r);
+            }
             st_out(at(io.done + row, i), (uint8_t)done);
         }
         if constexpr (GYMLIKE) {
             if (done && io.auto_reset) {
                 step = 0;
                 reset_any = true;
-                if constexpr (VAR == DR_VARIANT_GYM) {
+                if constexpr (GYMSTATE) {
                     gym_reset_regs(vk, i, 0, st, ep_num, eps, nd_ok ? &nd[0] : nullptr);
                     nd_ok = false;
+                    if constexpr (SMOOTH) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) fm[k] = kHover32;
+                    }
                 } else {
                     moving_reset_regs(vk, i, 0, st, cen, mp, ep_num, eps, nd_ok ? nd : nullptr);
                     nd_ok = false;
@@ -947,7 +1050,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 if (ep_num % 2000 == 0) eps += 0.1;
             }
         }
-        make_obs<S, OD>(st, ob, tvel);
+        make_obs<S, OD>(st, ob, ext);
         if (!live) {
 #pragma unroll
             for (int k = 0; k < OD; ++k) ob[k] = 0.f;
@@ -972,7 +1075,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                                            io.a_lo + io.a_span * u01_f32(r.w));
             if (io.act_out && live)
                 st_out(at(reinterpret_cast<float4 *>(io.act_out) + (int64_t)t * n_, i), act);
-            step_one(motor_mix(act), t);
+            step_one(mix_of(act), t);
         }
     } else {
         // Each action is loaded ahead into the registers the action two
@@ -1003,6 +1106,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
             for (int k = 0; k < 9; ++k) asm volatile("" ::"v"(mp[k]));
         }
+        if constexpr (SMOOTH) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(fm[k]));
+        }
         // Two steps ahead, in two registers that alternate (the loop is
         // unrolled by two so each keeps its role): step t's action was
         // loaded at the top of step t-2; younger than that load are step
@@ -1018,7 +1125,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 // done and NQ obs-row stores, step t - 1 the next load
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             }
-            const MotorMix mx = motor_mix(make_float4(r.x, r.y, r.z, r.w));
+            const MotorMix mx = mix_of(make_float4(r.x, r.y, r.z, r.w));
             asm volatile("" ::"v"(mx.thr), "v"(mx.phi), "v"(mx.theta), "v"(mx.psi));
             __builtin_amdgcn_sched_barrier(0);
             if (t + 2 < io.k) {
@@ -1040,8 +1147,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
         for (int k = 0; k < 12; ++k) st_out(at(fp.p[k], i), st[k]);
         st_out(at(fp.step, i), step);
+        if constexpr (SMOOTH) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
+        }
         if (reset_any) {
-            if constexpr (VAR == DR_VARIANT_GYM) {
+            if constexpr (GYMSTATE) {
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
             } else if constexpr (VAR == DR_VARIANT_MOVING) {
@@ -1726,7 +1837,7 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
                                                            const uint8_t *mask,
                                                            float *obs, int mode,
                                                            int init) {
-    constexpr int OD = VAR == DR_VARIANT_GYM ? 15 : (VAR == DR_VARIANT_MOVING ? 18 : 12);
+    constexpr int OD = od_of<VAR>();
     __shared__ float4 sh4[kBlock * OD / 4];
     const int64_t base = (int64_t)blockIdx.x * kBlock;
     const int64_t i = base + threadIdx.x;
@@ -1744,6 +1855,10 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
         if (doit) {
             if constexpr (VAR == DR_VARIANT_GYM) {
                 gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
+            } else if constexpr (VAR == DR_VARIANT_SMOOTH) {
+                gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v.mot[k * v.stride + i] = kHover32;
             } else if constexpr (VAR == DR_VARIANT_MOVING) {
                 float mp[9];
                 moving_reset_regs(v, i, mode, st, &st[F_TGT], mp, v.ep_num[i], v.eps[i]);
@@ -1767,7 +1882,14 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
             for (int k = 0; k < 9; ++k) mp[k] = v.mot[k * v.stride + i];
             moving_target(cen, mp, v.step[i], (float)v.dt, &st[F_TGT], tvel);
         }
-        make_obs<S, OD>(st, ob, tvel);
+        if constexpr (VAR == DR_VARIANT_SMOOTH) {
+            float fm[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) fm[k] = v.mot[k * v.stride + i];
+            make_obs<S, OD>(st, ob, fm);
+        } else {
+            make_obs<S, OD>(st, ob, tvel);
+        }
     } else {
 #pragma unroll
         for (int k = 0; k < OD; ++k) ob[k] = 0.f;
@@ -1850,6 +1972,23 @@ __global__ void set_field_kernel(EnvView<S> v, int field, const void *in) {
     }
 }
 
+// DR_FIELD_MOTOR (smooth variant), a kernel of its own so the field kernels
+// above stay as they were: row j of the (k,4) f32 buffer `io` is read from
+// (get: ids null, env j; gather: env ids[j]) or written to (set) the 4 motor
+// arrays at `mot`.
+__global__ void motor_field_kernel(float *mot, int64_t stride, int64_t n, const int32_t *ids,
+                                   int64_t k, float *io, int set) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const int64_t i = ids ? (int64_t)ids[j] : j;
+    if (i < 0 || i >= n) return;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (set) mot[c * stride + i] = io[j * 4 + c];
+        else io[j * 4 + c] = mot[c * stride + i];
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void random_actions_kernel(
     int64_t n, uint32_t k0, uint32_t k1, int64_t env_off, uint64_t step,
     float lo, float span, float4 *out) {
@@ -1881,6 +2020,9 @@ struct dr_handle {
     // twice the waves in flight); chosen by batch size in dr_create
     int rpw = 64;
     bool nt_loads = false;  // nontemporal state loads (large batches)
+    // DR_VARIANT_SMOOTH (dr_set_smoothing): passed to each launch
+    float alpha = 1.0f;
+    float rate_penalty = 0.0f;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -1914,8 +2056,9 @@ EnvView<S> view_of(const dr_handle *h) {
     v.ep_num = reinterpret_cast<int32_t *>(m + Layout<S>::ep_num(sp));
     v.ep_ret = reinterpret_cast<float *>(m + Layout<S>::ep_ret(sp));
     v.ep_len = reinterpret_cast<int32_t *>(m + Layout<S>::ep_len(sp));
-    v.mot = h->cfg.variant == DR_VARIANT_MOVING ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
-                                                 : nullptr;
+    v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH)
+                ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
+                : nullptr;
     v.n = h->n;
     v.env_id_offset = h->cfg.env_id_offset;
     v.host_u = h->host_u;
@@ -1928,11 +2071,20 @@ EnvView<S> view_of(const dr_handle *h) {
 
 size_t state_bytes(int64_t stride, int dtype, int variant) {
     const size_t s = dtype == DR_STATE_F64 ? sizeof(double) : sizeof(float);
-    const size_t mot = variant == DR_VARIANT_MOVING ? 9 * sizeof(float) : 0;
+    const size_t mot = variant == DR_VARIANT_MOVING
+                           ? 9 * sizeof(float)
+                           : (variant == DR_VARIANT_SMOOTH ? 4 * sizeof(float) : 0);
     return (size_t)F_N * stride * s + (size_t)stride * (8 + 4 + 4 + 4 + 4 + mot);
 }
 
 inline hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
+
+// The variant's trailing kernel argument (empty but for the smooth variant).
+template <int VAR>
+VarArgs<VAR> var_args(const dr_handle *h) {
+    if constexpr (VAR == DR_VARIANT_SMOOTH) return VarArgs<VAR>{h->alpha, h->rate_penalty};
+    else return VarArgs<VAR>{};
+}
 
 template <typename S, int VAR>
 int launch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
@@ -1955,6 +2107,9 @@ int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
     if (h->cfg.variant == DR_VARIANT_MOVING)
         return f64 ? launch_reset<double, DR_VARIANT_MOVING>(h, mask, obs, mode, init, st)
                    : launch_reset<float, DR_VARIANT_MOVING>(h, mask, obs, mode, init, st);
+    if (h->cfg.variant == DR_VARIANT_SMOOTH)
+        return f64 ? launch_reset<double, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st)
+                   : launch_reset<float, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st);
     return f64 ? launch_reset<double, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st)
                : launch_reset<float, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st);
 }
@@ -1967,16 +2122,17 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
     fp.step = v.step;
     fp.ep_num = v.ep_num;
     fp.eps = v.eps;
+    const VarArgs<VAR> va = var_args<VAR>(h);
     bool launched = false;
     if (!launched && VAR != DR_VARIANT_VECTORIZED && v.host_u) {   // parity mode
         if (h->rpw == 32)
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, true, false>),
                                dim3(grid_for(h->n, DR_ENV_WPB * 32)), dim3(kEnvBlock), 0, st,
-                               v, io, fp);
+                               v, io, fp, va);
         else
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 64, true, false>),
                                dim3(grid_for(h->n, DR_ENV_WPB * 64)), dim3(kEnvBlock), 0, st,
-                               v, io, fp);
+                               v, io, fp, va);
         launched = true;
     }
     if (!launched) {
@@ -1984,19 +2140,19 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
         switch (h->rpw * 2 + (int)h->nt_loads) {
             case 64:
                 hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, false, false>), g32,
-                                   dim3(kEnvBlock), 0, st, v, io, fp);
+                                   dim3(kEnvBlock), 0, st, v, io, fp, va);
                 break;
             case 65:
                 hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, false, true>), g32,
-                                   dim3(kEnvBlock), 0, st, v, io, fp);
+                                   dim3(kEnvBlock), 0, st, v, io, fp, va);
                 break;
             case 129:
                 hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 64, false, true>), g64,
-                                   dim3(kEnvBlock), 0, st, v, io, fp);
+                                   dim3(kEnvBlock), 0, st, v, io, fp, va);
                 break;
             default:
                 hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 64, false, false>), g64,
-                                   dim3(kEnvBlock), 0, st, v, io, fp);
+                                   dim3(kEnvBlock), 0, st, v, io, fp, va);
         }
     }
     hipError_t e = hipGetLastError();
@@ -2014,6 +2170,9 @@ int dispatch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
     if (h->cfg.variant == DR_VARIANT_MOVING)
         return f64 ? launch_step<double, DR_VARIANT_MOVING, MON>(h, io, st)
                    : launch_step<float, DR_VARIANT_MOVING, MON>(h, io, st);
+    if (h->cfg.variant == DR_VARIANT_SMOOTH)
+        return f64 ? launch_step<double, DR_VARIANT_SMOOTH, MON>(h, io, st)
+                   : launch_step<float, DR_VARIANT_SMOOTH, MON>(h, io, st);
     return f64 ? launch_step<double, DR_VARIANT_VECTORIZED, MON>(h, io, st)
                : launch_step<float, DR_VARIANT_VECTORIZED, MON>(h, io, st);
 }
@@ -2038,11 +2197,18 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
         const char *r = std::getenv("DRONERL_ROLLOUT_WS");
         return r ? (std::atoi(r) != 0 ? 1 : 0) : -1;
     }();
-    const bool ws = ws_env >= 0 ? ws_env == 1 : h->n <= (int64_t)kWsEnvs * device_cu_count();
+    // The smooth variant has the one-role kernel only (its lag state is not
+    // built into the warp-specialised forms), whatever the override says.
+    const bool ws = VAR == DR_VARIANT_SMOOTH
+                        ? false
+                        : (ws_env >= 0 ? ws_env == 1
+                                       : h->n <= (int64_t)kWsEnvs * device_cu_count());
     // with events: hipExtLaunchKernelGGL binds them to the dispatch packet's
     // own start / end timestamps (no extra packets in the queue)
     if (ws) {
-        if constexpr (VAR == DR_VARIANT_GYM && !GEN) {
+        if constexpr (VAR == DR_VARIANT_SMOOTH) {
+            // unreachable: ws is false for this variant
+        } else if constexpr (VAR == DR_VARIANT_GYM && !GEN) {
             // the split-physics form of the warp-specialised kernel (gym
             // variant, actions read from HBM; with the in-kernel policy its
             // memory waves' Philox draws share the SIMD with two physics
@@ -2068,10 +2234,10 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
         const dim3 grid(grid_for(h->n, DR_ENV_WPB * 64)), block(kEnvBlock);
         if (e0 || e1)
             hipExtLaunchKernelGGL((env_rollout_kernel<S, VAR, 64, GEN>), grid, block, 0, st, e0,
-                                  e1, 0, v, io, fp);
+                                  e1, 0, v, io, fp, var_args<VAR>(h));
         else
             hipLaunchKernelGGL((env_rollout_kernel<S, VAR, 64, GEN>), grid, block, 0, st, v, io,
-                               fp);
+                               fp, var_args<VAR>(h));
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -2089,8 +2255,29 @@ int dispatch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent
     if (h->cfg.variant == DR_VARIANT_MOVING)
         return f64 ? launch_rollout<double, DR_VARIANT_MOVING, GEN>(h, io, st, e0, e1)
                    : launch_rollout<float, DR_VARIANT_MOVING, GEN>(h, io, st, e0, e1);
+    if (h->cfg.variant == DR_VARIANT_SMOOTH)
+        return f64 ? launch_rollout<double, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1)
+                   : launch_rollout<float, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1);
     return f64 ? launch_rollout<double, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1)
                : launch_rollout<float, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1);
+}
+
+// DR_FIELD_MOTOR of dr_get_state / dr_gather_state / dr_set_state.
+int motor_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, float *io,
+                int set, void *stream) {
+    if (h->cfg.variant != DR_VARIANT_SMOOTH)
+        return fail(h, DR_ERR_INVALID,
+                    std::string(who) + ": motor exists only for DR_VARIANT_SMOOTH");
+    if (k == 0) return DR_OK;
+    DeviceGuard g(h->cfg.device);
+    float *mot = h->cfg.state_dtype == DR_STATE_F64 ? view_of<double>(h).mot
+                                                    : view_of<float>(h).mot;
+    hipLaunchKernelGGL(motor_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
+                       mot, h->stride, h->n, ids, k, io, set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return DR_OK;
 }
 
 int check_rng(dr_handle *h) {
@@ -2113,7 +2300,7 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     dr_config cfg = *cfg_in;
     if (cfg.num_envs < 1) return fail(nullptr, DR_ERR_INVALID, "dr_create: num_envs must be >= 1");
     if (cfg.variant != DR_VARIANT_GYM && cfg.variant != DR_VARIANT_VECTORIZED &&
-        cfg.variant != DR_VARIANT_MOVING)
+        cfg.variant != DR_VARIANT_MOVING && cfg.variant != DR_VARIANT_SMOOTH)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown variant");
     if (cfg.state_dtype != DR_STATE_F64 && cfg.state_dtype != DR_STATE_F32)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown state_dtype");
@@ -2142,7 +2329,11 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     // would put the 17 concurrently streamed arrays at congruent addresses
     // (same HBM channel bits); DR_STRIDE_PAD elements of skew break that.
     h->stride = (cfg.num_envs + 63) / 64 * 64 + DR_STRIDE_PAD;
-    h->obs_dim = cfg.variant == DR_VARIANT_GYM ? 15 : (cfg.variant == DR_VARIANT_MOVING ? 18 : 12);
+    h->obs_dim = cfg.variant == DR_VARIANT_GYM
+                     ? 15
+                     : (cfg.variant == DR_VARIANT_MOVING
+                            ? 18
+                            : (cfg.variant == DR_VARIANT_SMOOTH ? 19 : 12));
     // Launch form by batch size, from the measured sweep
     // (scripts/micro/ab_sweep.sh, profiles/r01_env_launch_sweep.txt):
     // [0, 384k) 64 rows/wave; [384k, 1.5M) 32 + nontemporal state loads;
@@ -2341,6 +2532,8 @@ int dr_rollout_random(dr_handle *h, int32_t k, uint64_t action_seed, int64_t act
 int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_state: null handle");
     if (!out) return fail(h, DR_ERR_INVALID, "dr_get_state: out is null");
+    if (field == DR_FIELD_MOTOR)
+        return motor_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)
@@ -2361,6 +2554,8 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
                     void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_gather_state: null handle");
     if (!env_ids || !out || k < 0) return fail(h, DR_ERR_INVALID, "dr_gather_state: bad arguments");
+    if (field == DR_FIELD_MOTOR)
+        return motor_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_gather_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)
@@ -2381,6 +2576,9 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
 int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_state: null handle");
     if (!in) return fail(h, DR_ERR_INVALID, "dr_set_state: in is null");
+    if (field == DR_FIELD_MOTOR)
+        return motor_field(h, "dr_set_state", nullptr, h->n,
+                           const_cast<float *>(static_cast<const float *>(in)), 1, stream);
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)
@@ -2408,6 +2606,28 @@ int dr_set_reset_uniforms(dr_handle *h, const double *u_dev) {
 int dr_set_seed(dr_handle *h, uint64_t seed) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_seed: null handle");
     h->cfg.seed = seed;
+    return DR_OK;
+}
+
+int dr_set_smoothing(dr_handle *h, float alpha, float rate_penalty) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_smoothing: null handle");
+    // written so that NaN fails every test
+    if (!(alpha > 0.0f && alpha <= 1.0f))
+        return fail(h, DR_ERR_INVALID, "dr_set_smoothing: alpha must be in (0, 1]");
+    if (!(rate_penalty >= 0.0f && rate_penalty <= 3.4028234663852886e38f))
+        return fail(h, DR_ERR_INVALID, "dr_set_smoothing: rate_penalty must be finite and >= 0");
+    if (h->cfg.variant != DR_VARIANT_SMOOTH)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_smoothing: only DR_VARIANT_SMOOTH has a motor lag");
+    h->alpha = alpha;
+    h->rate_penalty = rate_penalty;
+    return DR_OK;
+}
+
+int dr_get_smoothing(const dr_handle *h, float *alpha, float *rate_penalty) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_smoothing: null handle");
+    if (h->cfg.variant != DR_VARIANT_SMOOTH) return DR_ERR_UNSUPPORTED;
+    if (alpha) *alpha = h->alpha;
+    if (rate_penalty) *rate_penalty = h->rate_penalty;
     return DR_OK;
 }
 

@@ -2436,11 +2436,11 @@ static int launch_linear_tanh(const char *who, int nets, int64_t m, int64_t k, i
                            m, (int)n, x, rows, lp, X6Aux{});                               \
         break;
         DR_LT_CASE(4) DR_LT_CASE(8) DR_LT_CASE(12) DR_LT_CASE(15) DR_LT_CASE(16)
-        DR_LT_CASE(18) DR_LT_CASE(24) DR_LT_CASE(32)
+        DR_LT_CASE(18) DR_LT_CASE(19) DR_LT_CASE(24) DR_LT_CASE(32)
 #undef DR_LT_CASE
         default:
             return fail0(DR_ERR_UNSUPPORTED,
-                         std::string(who) + ": k must be one of 4, 8, 12, 15, 16, 18, 24, 32");
+                         std::string(who) + ": k must be one of 4, 8, 12, 15, 16, 18, 19, 24, 32");
     }
     return check_launch(who);
 }
@@ -2631,11 +2631,11 @@ static int launch_first_bwd(const char *who, int nets, int64_t m, int64_t k, int
                            m, (int)n, in, x, rows, part);                                  \
         break;
         DR_FL_CASE(4) DR_FL_CASE(8) DR_FL_CASE(12) DR_FL_CASE(15) DR_FL_CASE(16)
-        DR_FL_CASE(18) DR_FL_CASE(24) DR_FL_CASE(32)
+        DR_FL_CASE(18) DR_FL_CASE(19) DR_FL_CASE(24) DR_FL_CASE(32)
 #undef DR_FL_CASE
         default:
             return fail0(DR_ERR_UNSUPPORTED,
-                         std::string(who) + ": k must be one of 4, 8, 12, 15, 16, 18, 24, 32");
+                         std::string(who) + ": k must be one of 4, 8, 12, 15, 16, 18, 19, 24, 32");
     }
     int rc = check_launch(who);
     if (rc) return rc;

@@ -25,13 +25,31 @@ ARM_LENGTH = 0.5
 K_YAW = 0.01
 MAX_STEPS = 200
 MOTOR_MAX = 3 * MASS * G / 4.0          # 7.3575, action_space.high
-OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18}
+OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18, "smooth": 19}
+# the force each motor applies after a reset of the "smooth" variant
+# (DESIGN.md section 14): f32(mass * g / 4)
+HOVER = float(np.float32(MASS * G / 4.0))
 # reset uniforms per env and reset for rng="host" 
-RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14}
+RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14, "smooth": 5}
 _VARIANT_ID = {"gym": _lib.DR_VARIANT_GYM, "vectorized": _lib.DR_VARIANT_VECTORIZED,
-               "moving": _lib.DR_VARIANT_MOVING}
+               "moving": _lib.DR_VARIANT_MOVING, "smooth": _lib.DR_VARIANT_SMOOTH}
 
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
+# (N, width) f32 fields a single variant owns
+_F32_ROW_FIELDS = {"motion": 9, "motor": 4}
+
+
+def check_smoothing(variant: str, motor_alpha: float, rate_penalty: float) -> None:
+    """The argument rules of dr_set_smoothing, raised as ValueError before any
+    device work: alpha in (0, 1], rate_penalty finite and >= 0, and both at
+    their neutral values (1, 0) on every variant but "smooth"."""
+    a, lam = float(motor_alpha), float(rate_penalty)
+    if not (0.0 < a <= 1.0):
+        raise ValueError(f"motor_alpha must be in (0, 1], got {motor_alpha!r}")
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"rate_penalty must be finite and >= 0, got {rate_penalty!r}")
+    if variant != "smooth" and (a != 1.0 or lam != 0.0):
+        raise ValueError(f"motor_alpha / rate_penalty need variant='smooth', not {variant!r}")
 
 
 def _stream(device):
@@ -44,20 +62,28 @@ class DroneBatch:
     variant    "gym" (DroneGymEnv, drone.py), "vectorized"
                (VectorizedDroneEnv, vectorized_drone.py) or "moving" (the
                moving-target curriculum of BASELINE configs[4]; 18-d obs)
+               or "smooth" (the gym env behind a first-order motor lag with
+               an action-rate penalty; 19-d obs)
     dtype      torch.float64 (reference precision) or torch.float32 state
     rng        "philox" (counter-based, seeded) or "host" (caller supplies
                the reset uniforms: numpy-MT19937 replay for parity tests)
     auto_reset DummyVecEnv semantics: a done env is reset inside the step
                and obs holds the reset observation.
+    motor_alpha, rate_penalty
+               "smooth" only: the lag blend alpha = dt / (tau + dt) in (0, 1]
+               and the penalty on |command - motor force|^2 (>= 0).  At the
+               defaults (1, 0) the variant is "gym" bit for bit.
     """
 
     def __init__(self, num_envs: int, variant: str = "gym",
                  dtype: torch.dtype = torch.float64, device=None, seed: int = 0,
                  auto_reset: bool = True, rng: str = "philox",
                  env_id_offset: int = 0, max_steps: int | None = None,
-                 keep_terminal_obs: bool = False, monitor: bool = False):
+                 keep_terminal_obs: bool = False, monitor: bool = False,
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
+        check_smoothing(variant, motor_alpha, rate_penalty)
         if dtype not in (torch.float64, torch.float32):
             raise ValueError("dtype must be torch.float64 or torch.float32")
         if rng not in ("philox", "host"):
@@ -98,6 +124,9 @@ class DroneBatch:
         self.ep_ret = torch.zeros(n, dtype=torch.float32, device=dev) if monitor else None
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev) if monitor else None
         self._uniforms = None
+        self.motor_alpha, self.rate_penalty = 1.0, 0.0
+        if variant == "smooth":
+            self.set_smoothing(motor_alpha, rate_penalty)
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -263,8 +292,8 @@ class DroneBatch:
             return torch.empty(n, dtype=torch.float64, **where)
         if field == "ep_return":
             return torch.empty(n, dtype=torch.float32, **where)
-        if field == "motion":
-            return torch.empty(n, 9, dtype=torch.float32, **where)
+        if field in _F32_ROW_FIELDS:
+            return torch.empty(n, _F32_ROW_FIELDS[field], dtype=torch.float32, **where)
         return torch.empty(n, dtype=torch.int32, **where)
 
     def get(self, field: str) -> torch.Tensor:
@@ -287,7 +316,8 @@ class DroneBatch:
 
     def gather(self, field: str, env_ids: torch.Tensor, out: torch.Tensor | None = None):
         """`get(field)` for the envs in env_ids (int32 device tensor), into
-        `out` if given (k,3) f64 / (k,) / (k,9) f32 for "motion"."""
+        `out` if given (k,3) f64 / (k,) / (k,9) f32 for "motion" / (k,4) f32 for
+        "motor"."""
         fid = _lib.FIELDS[field]
         k = env_ids.numel()
         if out is None:
@@ -297,8 +327,9 @@ class DroneBatch:
                 out = torch.empty(k, dtype=torch.float64, device=self.device)
             elif field == "ep_return":
                 out = torch.empty(k, dtype=torch.float32, device=self.device)
-            elif field == "motion":
-                out = torch.empty(k, 9, dtype=torch.float32, device=self.device)
+            elif field in _F32_ROW_FIELDS:
+                out = torch.empty(k, _F32_ROW_FIELDS[field], dtype=torch.float32,
+                                  device=self.device)
             else:
                 out = torch.empty(k, dtype=torch.int32, device=self.device)
         ids = env_ids.to(device=self.device, dtype=torch.int32).contiguous()
@@ -314,8 +345,8 @@ class DroneBatch:
             dt, shape = torch.float64, (self.num_envs,)
         elif field == "ep_return":
             dt, shape = torch.float32, (self.num_envs,)
-        elif field == "motion":
-            dt, shape = torch.float32, (self.num_envs, 9)
+        elif field in _F32_ROW_FIELDS:
+            dt, shape = torch.float32, (self.num_envs, _F32_ROW_FIELDS[field])
         else:
             dt, shape = torch.int32, (self.num_envs,)
         v = torch.as_tensor(value, dtype=dt).to(self.device).reshape(shape).contiguous()
@@ -326,6 +357,17 @@ class DroneBatch:
         """New Philox key for every later reset (order-free per env)."""
         self.seed_value = int(seed)
         check(self.L.dr_set_seed(self.handle, self.seed_value & (2**64 - 1)), self.handle)
+
+    def set_smoothing(self, motor_alpha: float, rate_penalty: float) -> None:
+        """variant="smooth": new lag blend and action-rate penalty for every
+        step / rollout enqueued after the call (a captured graph keeps the
+        values it was captured with)."""
+        if self.variant != "smooth":
+            raise ValueError(f"set_smoothing needs variant='smooth', not {self.variant!r}")
+        check_smoothing(self.variant, motor_alpha, rate_penalty)
+        check(self.L.dr_set_smoothing(self.handle, float(motor_alpha), float(rate_penalty)),
+              self.handle)
+        self.motor_alpha, self.rate_penalty = float(motor_alpha), float(rate_penalty)
 
     def set_reset_uniforms(self, u) -> None:
         """rng='host': (N,5) f64 uniforms ((N,14) for "moving") consumed by

@@ -89,6 +89,15 @@ class PPOConfig:
     # the 200-step limit (drone.py:155-157, no crash) add gamma * V(terminal
     # obs) to that step's reward.  Off = the reference's semantics
     bootstrap_timeouts: bool = False
+    # variant "smooth" (DESIGN.md section 14): the motor-lag blend alpha =
+    # dt / (tau + dt) in (0, 1] and the penalty on |command - motor force|^2.
+    # The neutral values (1, 0) are the gym env; anything else needs the variant
+    motor_alpha: float = 1.0
+    rate_penalty: float = 0.0
+
+    def __post_init__(self):
+        from .env import check_smoothing
+        check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -118,7 +127,8 @@ class PPOTrainer:
         self.env = DroneBatch(N, cfg.variant, device=dev, seed=cfg.seed,
                               env_id_offset=D.env_shard(rank, N)[0], monitor=True,
                               keep_terminal_obs=cfg.bootstrap_timeouts,
-                              dtype=torch.float64 if cfg.state_dtype == "f64" else torch.float32)
+                              dtype=torch.float64 if cfg.state_dtype == "f64" else torch.float32,
+                              motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty)
         if cfg.initial_eps:
             self.env.set("eps", torch.full((N,), float(cfg.initial_eps), dtype=torch.float64))
         od = self.env.obs_dim
@@ -306,7 +316,8 @@ class PPOTrainer:
         as on the eager path."""
         c = self.cfg
         if kind == "rollout":
-            return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps)
+            return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
+                    self.env.motor_alpha, self.env.rate_penalty)
         o = self.opt
         return (c.seed, self.rank, c.n_epochs, c.batch_size, c.clip_range, c.ent_coef,
                 c.vf_coef, c.normalize_advantage, float(o.lr), o.b1, o.b2, o.eps,
@@ -555,7 +566,8 @@ class PPOTrainer:
                    "ep_return", "ep_length")
 
     def _env_fields(self):
-        return self._ENV_FIELDS + (("motion",) if self.cfg.variant == "moving" else ())
+        return self._ENV_FIELDS + {"moving": ("motion",),
+                                   "smooth": ("motor",)}.get(self.cfg.variant, ())
 
     def state_dict(self):
         """Everything needed to resume bit-for-bit on the same device count:

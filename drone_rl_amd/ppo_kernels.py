@@ -245,7 +245,7 @@ class ClipAdam:
         return self.grad_norm
 
 
-LINEAR_TANH_K = (4, 8, 12, 15, 16, 18, 24, 32)
+LINEAR_TANH_K = (4, 8, 12, 15, 16, 18, 19, 24, 32)
 
 
 def _rows(rows):

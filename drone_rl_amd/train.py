@@ -61,8 +61,13 @@ def main(argv=None):
     ap.add_argument("--net", type=int, nargs="+", default=[256, 256])
     ap.add_argument("--state-dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--variant", choices=["gym", "moving"], default="gym",
-                    help="gym = DroneGymEnv; moving = the moving-target curriculum")
+    ap.add_argument("--variant", choices=["gym", "moving", "smooth"], default="gym",
+                    help="gym = DroneGymEnv; moving = the moving-target curriculum; "
+                         "smooth = gym behind a motor lag with an action-rate penalty")
+    ap.add_argument("--motor-alpha", type=float, default=1.0,
+                    help="--variant smooth: lag blend dt / (tau + dt) in (0, 1] (1 = no lag)")
+    ap.add_argument("--rate-penalty", type=float, default=0.0,
+                    help="--variant smooth: penalty on |command - motor force|^2 per step")
     ap.add_argument("--sb3-defaults", action="store_true",
                     help="SB3 PPO defaults of the reference (n_steps 2048, batch 64, 64x64)")
     ap.add_argument("--checkpoint", default="./dd_gpu.pt")
@@ -97,6 +102,7 @@ def main(argv=None):
                   grad_buckets=a.grad_buckets,
                   state_dtype=a.state_dtype, variant=a.variant, initial_eps=a.initial_eps,
                   bootstrap_timeouts=a.bootstrap_timeouts,
+                  motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

@@ -34,7 +34,8 @@ try:  # optional: let SB3's isinstance(env, VecEnv) checks pass
 except Exception:  # noqa: BLE001 - SB3 absent (this image)
     _VecEnvBase = object
 
-_STATE = ("pos", "vel", "euler", "omega", "target")
+# "motor": the smooth variant's motor forces (DroneBatch raises on the others)
+_STATE = ("pos", "vel", "euler", "omega", "target", "motor")
 _SCALAR = {"current_step": int, "ep_num": int, "eps": float}
 
 
@@ -46,13 +47,15 @@ class BatchedDroneVecEnv(_VecEnvBase):
 
     def __init__(self, num_envs: int = 1, variant: str = "gym",
                  dtype: torch.dtype = torch.float64, device=None, seed: int | None = None,
-                 monitor: bool = True, rng: str = "philox", env_id_offset: int = 0):
+                 monitor: bool = True, rng: str = "philox", env_id_offset: int = 0,
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=(variant != "vectorized"), rng=rng,
                                 env_id_offset=env_id_offset, keep_terminal_obs=True,
-                                monitor=True)
+                                monitor=True, motor_alpha=motor_alpha,
+                                rate_penalty=rate_penalty)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -119,6 +122,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
 
     def get_attr(self, attr_name, indices=None):
         idx = self._indices(indices)
+        if attr_name == "motor" and self.batch.variant != "smooth":
+            raise AttributeError("only the 'smooth' variant has attribute 'motor'")
         if attr_name in _STATE:
             v = self.batch.get_host(attr_name)
             return [v[i].copy() for i in idx]
@@ -174,6 +179,7 @@ class DroneVectorEnv:
     """gymnasium-1.x-style vector facade (same-step autoreset).
 
     reset(seed=None, options=None) -> (obs (N,15) f32, infos dict)
+    ((N,19) with variant="smooth": the gym obs plus the four motor forces)
     step(actions) -> (obs, rewards f32, terminated bool, truncated bool, infos)
 
     terminated/truncated follow the reference as shimmy converts it: the
@@ -190,13 +196,18 @@ class DroneVectorEnv:
 
     def __init__(self, num_envs: int, device=None, seed: int = 0,
                  dtype: torch.dtype = torch.float64, split_time_limit: bool = False,
-                 as_tensors: bool = False):
-        self.batch = DroneBatch(num_envs, "gym", dtype=dtype, device=device, seed=seed,
-                                auto_reset=True, keep_terminal_obs=True, monitor=True)
+                 as_tensors: bool = False, variant: str = "gym",
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
+        if variant not in ("gym", "smooth"):
+            raise ValueError("DroneVectorEnv wraps the 'gym' or 'smooth' variant")
+        self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
+                                auto_reset=True, keep_terminal_obs=True, monitor=True,
+                                motor_alpha=motor_alpha, rate_penalty=rate_penalty)
         self.num_envs = num_envs
-        self.single_observation_space = make_box(-np.inf, np.inf, (15,), np.float32)
+        od = self.batch.obs_dim
+        self.single_observation_space = make_box(-np.inf, np.inf, (od,), np.float32)
         self.single_action_space = make_box(0, MOTOR_MAX, (4,), np.float32)
-        self.observation_space = make_box(-np.inf, np.inf, (num_envs, 15), np.float32)
+        self.observation_space = make_box(-np.inf, np.inf, (num_envs, od), np.float32)
         self.action_space = make_box(0, MOTOR_MAX, (num_envs, 4), np.float32)
         self.split_time_limit = split_time_limit
         self.as_tensors = as_tensors

@@ -58,7 +58,16 @@ enum dr_variant {
        c_k + a_k sin(w_k t + ph_k) with per-episode (a, w, ph), a = eps * U,
        so eps = 0 reproduces DR_VARIANT_GYM exactly; obs (N,18) = gym obs +
        target velocity; reward = the gym reward against the moving target. */
-    DR_VARIANT_MOVING = 2
+    DR_VARIANT_MOVING = 2,
+    /* Smooth control (an extension with no reference oracle, spec in
+       DESIGN.md section 14): the gym env with a first-order motor lag and an
+       action-rate penalty.  Per env the force f each motor applies is state
+       (DR_FIELD_MOTOR, HOVER = f32(9.81 / 4) after every reset); a step with
+       command a forms, in f32, s = |a - f|^2, f' = (1 - alpha) f + alpha a,
+       runs the gym step on f' and reports reward - rate_penalty * s;
+       obs (N,19) = gym obs + f'.  alpha / rate_penalty: dr_set_smoothing;
+       at their defaults (1, 0) the variant is DR_VARIANT_GYM bit for bit. */
+    DR_VARIANT_SMOOTH = 3
 };
 
 enum dr_state_dtype {
@@ -90,8 +99,10 @@ enum dr_field {   /* dr_get_state / dr_set_state, all device buffers      */
     DR_FIELD_EPS = 7,       /* (N,)  f64  curriculum eps (drone.py:33,70)    */
     DR_FIELD_EP_RETURN = 8, /* (N,)  f32  running episode return (monitor)   */
     DR_FIELD_EP_LENGTH = 9, /* (N,)  i32  running episode length (monitor)   */
-    DR_FIELD_MOTION = 10    /* (N,9) f32  moving variant: a xyz, w xyz, ph xyz
+    DR_FIELD_MOTION = 10,   /* (N,9) f32  moving variant: a xyz, w xyz, ph xyz
                                (DR_FIELD_TARGET is then the motion centre)  */
+    DR_FIELD_MOTOR = 11     /* (N,4) f32  smooth variant: the force each motor
+                               applies (the lag filter's state)             */
 };
 
 typedef struct dr_config {
@@ -127,7 +138,7 @@ int dr_create(const dr_config *cfg, dr_handle **out);
 int dr_destroy(dr_handle *h);
 
 int64_t dr_num_envs(const dr_handle *h);
-int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving */
+int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving, 19 smooth */
 
 /* Reset every env and write (N,obs_dim) obs.  Replaces DroneEnv.reset
    (drone.py:48-75) called on each env by VecEnv.reset, and
@@ -178,7 +189,7 @@ int dr_step_monitored_trunc(dr_handle *h, const float *actions, float *obs_out,
 /* Device-side state access (parity injection, checkpointing, get_attr). */
 int dr_get_state(dr_handle *h, int field, void *out, void *stream);
 /* dr_get_state for k selected envs: out row j = field of env env_ids[j]
-   ((k,3) f64 for vector fields, (k,) for scalars, (k,9) f32 for MOTION).
+   ((k,3) f64 for vector fields, (k,) for scalars, (k,9) f32 for MOTION, (k,4) f32 for MOTOR).
    The per-step `get_attr('pos')` of TrajectoryTensorboardCallback
    (traj_tb.py:34) without copying the whole batch. */
 int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k,
@@ -194,6 +205,15 @@ int dr_set_reset_uniforms(dr_handle *h, const double *u_dev);
 /* Replace the Philox key used by later resets (VecEnv.seed).  Takes effect
    for work enqueued after the call. */
 int dr_set_seed(dr_handle *h, uint64_t seed);
+
+/* DR_VARIANT_SMOOTH: the lag blend alpha = dt / (tau + dt) in (0, 1] and the
+   action-rate penalty rate_penalty >= 0 (defaults 1 and 0: the gym env).
+   DR_ERR_INVALID for a null handle, values out of range or non-finite;
+   DR_ERR_UNSUPPORTED on the other variants.  Takes effect for work enqueued
+   after the call (the two values are launch arguments, not device state).
+   dr_get_smoothing reads them back (either pointer may be NULL). */
+int dr_set_smoothing(dr_handle *h, float alpha, float rate_penalty);
+int dr_get_smoothing(const dr_handle *h, float *alpha, float *rate_penalty);
 
 /* Synthetic random policy: out (n,4) f32 i.i.d. U[lo,hi) from Philox keyed
    by seed with counter (env_id_offset + i, step).  Not part of the
@@ -339,7 +359,7 @@ int dr_tanh_backward(int64_t m, int64_t n, const float *grad_h, const float *h,
 
 /* First MLP layer forward fused with its activation: h = tanh(x W^T + b)
    for x (m,k), W (n,k), b (n), h (m,n) (SB3 MlpExtractor's Linear + Tanh,
-   the narrow-input layer).  k in {4,8,12,15,16,18,24,32}; n % 4 == 0,
+   the narrow-input layer).  k in {4,8,12,15,16,18,19,24,32}; n % 4 == 0,
    n <= 256; h 16-byte aligned.  Replaces an addmm plus a separate tanh pass
    over the (m,n) activation.  `rows` (nullable, m int32): input row r is
    x[rows[r]] -- a minibatch read in place from the rollout buffer through

@@ -4,8 +4,16 @@ a fixed curriculum level, the way the reference's test.py does
 action space) and with sampled actions (the training-time policy), for S
 steps with DummyVecEnv auto-reset.  Prints one JSON line: mean return and
 length of the episodes that ended, the fraction of steps inside the 5 cm
-bonus radius, and the fraction of episodes that ended by crashing (before
-the 200-step limit).
+bonus radius, the fraction of episodes that ended by crashing (before
+the 200-step limit), and cmd_dev_sq_mean: the mean over env-steps of
+|command - motor force|^2 (N^2), how abruptly the policy drives the motors.
+
+A checkpoint trained on variant "smooth" is evaluated on that variant with
+the motor_alpha / rate_penalty of its config (the motor force is the env's
+lagged one, obs[:, 15:19]).  For a gym checkpoint the motors follow the
+command at once, so the force before a step is the previous clipped command,
+or HOVER on the first step of an episode -- what the smooth variant holds at
+its neutral parameters.
 
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
 """
@@ -20,7 +28,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import MOTOR_MAX  # noqa: E402
+from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM  # noqa: E402
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
@@ -29,9 +37,14 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
-    pol = ActorCritic(15, 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
+    smooth = cfg.get("variant", "gym") == "smooth"
+    variant = "smooth" if smooth else "gym"
+    alpha = float(cfg.get("motor_alpha", 1.0)) if smooth else 1.0
+    lam = float(cfg.get("rate_penalty", 0.0)) if smooth else 0.0
+    pol = ActorCritic(OBS_DIM[variant], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
     pol.flat.data.copy_(sd["flat"].to(dev))
-    env = DroneBatch(envs, "gym", device=dev, seed=seed, env_id_offset=1 << 40, monitor=True)
+    env = DroneBatch(envs, variant, device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
+                     motor_alpha=alpha, rate_penalty=lam)
     env.set("eps", torch.full((envs,), float(eps), dtype=torch.float64))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
@@ -39,6 +52,9 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
     std = pol.log_std.exp()
     ret_sum = len_sum = n_done = n_crash = 0.0
     in_bonus = 0.0
+    dev_sq = 0.0
+    # the force each motor applies before the step (gym: tracked here)
+    force = torch.full((envs, 4), HOVER, device=dev)
     ep_ret = torch.empty(envs, device=dev)
     ep_len = torch.empty(envs, dtype=torch.int32, device=dev)
     for _ in range(steps):
@@ -46,9 +62,15 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
         a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
                                                                  device=dev)
         env.ep_ret, env.ep_len = ep_ret, ep_len
-        o, r, d = env.step(a.clamp(0.0, MOTOR_MAX).contiguous())
+        cmd = a.clamp(0.0, MOTOR_MAX).contiguous()
+        if smooth:
+            force = obs[:, 15:19]
+        dev_sq += float(((cmd - force) ** 2).sum(1).mean())
+        o, r, d = env.step(cmd)
         obs = o.clone()
         db = d.bool()
+        if not smooth:
+            force = torch.where(db[:, None], torch.full_like(cmd, HOVER), cmd)
         in_bonus += float((r > 0).float().mean())      # +1 - 0.01 d > 0 only within 5 cm
         n_done += float(db.sum())
         ret_sum += float(ep_ret[db].sum())
@@ -58,7 +80,8 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
     n = max(n_done, 1.0)
     return {"deterministic": deterministic, "episodes": int(n_done),
             "ep_rew_mean": ret_sum / n, "ep_len_mean": len_sum / n,
-            "crash_frac": n_crash / n, "bonus_step_frac": in_bonus / steps}
+            "crash_frac": n_crash / n, "bonus_step_frac": in_bonus / steps,
+            "cmd_dev_sq_mean": dev_sq / steps}
 
 
 def main():
@@ -70,6 +93,11 @@ def main():
     ap.add_argument("--seed", type=int, default=123)
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
+    cfg = torch.load(a.ckpt, map_location="cpu", weights_only=True)["config"]
+    out["variant"] = cfg.get("variant", "gym")
+    if out["variant"] == "smooth":
+        out["motor_alpha"] = cfg.get("motor_alpha", 1.0)
+        out["rate_penalty"] = cfg.get("rate_penalty", 0.0)
     for det in (True, False):
         out["deterministic" if det else "sampled"] = evaluate(a.ckpt, a.eps, a.envs, a.steps,
                                                                a.seed, det)
