@@ -118,19 +118,28 @@ enum : uint32_t {
 // exact quotient, scripts/micro/tanh_rat.py), half the VALU of the two-form
 // evaluation.  The clamp is NaN-propagating (IEEE maximum / minimum), so NaN
 // stays NaN; +-inf -> +-tanh(7.905) (1 - 3 ulp).
+// Both polynomials carry a common factor kTanhScale = 2^8 (exact: every
+// coefficient and every fma scales by a power of two, and so does the rcp), so
+// that x P' ~ 1.25 x stays normal whenever x is: with the unscaled P(0) = 4.9e-3
+// the product x P underflowed to a subnormal for |x| < 2.4e-36 and the result
+// lost up to 103 ulp there (measured on the device against f64,
+// tests/test_tanh_device_gpu.py).  Everywhere else the result bits are those of
+// the unscaled form.
+constexpr float kTanhScale = 256.0f;
 __device__ inline float tanh_rat(float x) {
+    constexpr float S = kTanhScale;
     const float c = 7.90531110763549805f;
     const float xc = __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -c), c);
     const float s = xc * xc;
-    float p = fmaf(s, -2.76076847742355e-16f, 2.00018790482477e-13f);
-    p = fmaf(s, p, -8.60467152213735e-11f);
-    p = fmaf(s, p, 5.12229709037114e-08f);
-    p = fmaf(s, p, 1.48572235717979e-05f);
-    p = fmaf(s, p, 6.37261928875436e-04f);
-    p = fmaf(s, p, 4.89352455891786e-03f);
-    float q = fmaf(s, 1.19825839466702e-06f, 1.18534705686654e-04f);
-    q = fmaf(s, q, 2.26843463243900e-03f);
-    q = fmaf(s, q, 4.89352518554385e-03f);
+    float p = fmaf(s, S * -2.76076847742355e-16f, S * 2.00018790482477e-13f);
+    p = fmaf(s, p, S * -8.60467152213735e-11f);
+    p = fmaf(s, p, S * 5.12229709037114e-08f);
+    p = fmaf(s, p, S * 1.48572235717979e-05f);
+    p = fmaf(s, p, S * 6.37261928875436e-04f);
+    p = fmaf(s, p, S * 4.89352455891786e-03f);
+    float q = fmaf(s, S * 1.19825839466702e-06f, S * 1.18534705686654e-04f);
+    q = fmaf(s, q, S * 2.26843463243900e-03f);
+    q = fmaf(s, q, S * 4.89352518554385e-03f);
     return (xc * p) * __builtin_amdgcn_rcpf(q);
 }
 
@@ -142,19 +151,20 @@ __device__ inline f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
     return __builtin_elementwise_fma(a, b, c);
 }
 __device__ inline f32x2 tanh_rat2(f32x2 x) {
+    constexpr float S = kTanhScale;
     const f32x2 c = {7.90531110763549805f, 7.90531110763549805f};
     const f32x2 xc = __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -c), c);
     const f32x2 s = xc * xc;
     auto k = [](float v) { return f32x2{v, v}; };
-    f32x2 p = pk_fma(s, k(-2.76076847742355e-16f), k(2.00018790482477e-13f));
-    p = pk_fma(s, p, k(-8.60467152213735e-11f));
-    p = pk_fma(s, p, k(5.12229709037114e-08f));
-    p = pk_fma(s, p, k(1.48572235717979e-05f));
-    p = pk_fma(s, p, k(6.37261928875436e-04f));
-    p = pk_fma(s, p, k(4.89352455891786e-03f));
-    f32x2 q = pk_fma(s, k(1.19825839466702e-06f), k(1.18534705686654e-04f));
-    q = pk_fma(s, q, k(2.26843463243900e-03f));
-    q = pk_fma(s, q, k(4.89352518554385e-03f));
+    f32x2 p = pk_fma(s, k(S * -2.76076847742355e-16f), k(S * 2.00018790482477e-13f));
+    p = pk_fma(s, p, k(S * -8.60467152213735e-11f));
+    p = pk_fma(s, p, k(S * 5.12229709037114e-08f));
+    p = pk_fma(s, p, k(S * 1.48572235717979e-05f));
+    p = pk_fma(s, p, k(S * 6.37261928875436e-04f));
+    p = pk_fma(s, p, k(S * 4.89352455891786e-03f));
+    f32x2 q = pk_fma(s, k(S * 1.19825839466702e-06f), k(S * 1.18534705686654e-04f));
+    q = pk_fma(s, q, k(S * 2.26843463243900e-03f));
+    q = pk_fma(s, q, k(S * 4.89352518554385e-03f));
     const f32x2 r = {__builtin_amdgcn_rcpf(q.x), __builtin_amdgcn_rcpf(q.y)};
     return (xc * p) * r;
 }

@@ -151,6 +151,34 @@ def philox_np(ctr, key):
     return np.stack([x, y, z, w], 1).astype(np.uint32)
 
 
+def policy_noise_np(n, seed, counter):
+    """dr_policy_sample's standard-normal draws restated: row i is the Philox
+    block of counter (i, counter, TAG_NORMAL) under key seed; words x, y give
+    z0, z1 and words z, w give z2, z3 by Box-Muller.  The uniforms u1 =
+    ((a >> 8) + 1) 2^-24 in (0, 1], u2 = (b >> 8) 2^-24 and the angle theta =
+    f32(f32(2 pi) u2) are formed in f32 exactly as box_muller forms them (exact,
+    exact, one rounding); the radius sqrt(-2 ln u1) and cos / sin theta are
+    f64.  Returns (z (n, 4), radius (n, 4)) f64, the radius being that of the
+    element's pair."""
+    i = np.arange(n, dtype=np.uint64)
+    ctr = np.stack([i & np.uint64(0xffffffff), i >> np.uint64(32),
+                    np.full(n, counter & 0xffffffff, np.uint64),
+                    np.full(n, 0x4E000000 ^ (counter >> 32), np.uint64)], 1)
+    r = philox_np(ctr, [seed & 0xffffffff, seed >> 32])
+    z = np.zeros((n, 4))
+    rad = np.zeros((n, 4))
+    scale = np.float32(2.0 ** -24)
+    for p in range(2):
+        a, b = r[:, 2 * p], r[:, 2 * p + 1]
+        u1 = ((a >> np.uint32(8)).astype(np.float32) + np.float32(1.0)) * scale
+        u2 = (b >> np.uint32(8)).astype(np.float32) * scale
+        theta = (np.float32(6.2831853071795864769) * u2).astype(np.float64)
+        rr = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+        z[:, 2 * p], z[:, 2 * p + 1] = rr * np.cos(theta), rr * np.sin(theta)
+        rad[:, 2 * p] = rad[:, 2 * p + 1] = rr
+    return z, rad
+
+
 def permutation_np(n, seed, counter):
     """dr_permutation's result restated: the stable argsort of the 64-bit
     Philox keys (r.x << 32 | r.y) of counters (i, counter, TAG_PERM)."""

@@ -171,6 +171,34 @@ def test_philox_known_answers():
         np.testing.assert_array_equal(cref.philox(c, k), np.array(want, np.uint32))
 
 
+def test_policy_noise_known_answers():
+    """cref.policy_noise_np (the oracle of dr_policy_sample's draws): row 3 of
+    seed 0x1234567890, counter (7 << 32) + 5 (both high words live) against a
+    scalar Box-Muller of the C oracle's Philox block of that counter, and
+    against the recorded values."""
+    import math
+    seed, counter = 0x1234567890, (7 << 32) + 5
+    z, rad = cref.policy_noise_np(5, seed, counter)
+    w = cref.philox([3, 0, 5, 0x4E000000 ^ 7], [seed & 0xffffffff, seed >> 32])
+    assert [int(x) for x in w] == [0x7ea9aeab, 0x8e7f3e80, 0xc15ba444, 0x9cf5c066]
+    for p in range(2):
+        a, b = int(w[2 * p]), int(w[2 * p + 1])
+        u1 = ((a >> 8) + 1) / 2.0 ** 24
+        theta = float(np.float32(6.2831853071795864769) * np.float32((b >> 8) / 2.0 ** 24))
+        r = math.sqrt(-2.0 * math.log(u1))
+        assert rad[3, 2 * p] == rad[3, 2 * p + 1] == pytest.approx(r, rel=1e-15)
+        assert z[3, 2 * p] == pytest.approx(r * math.cos(theta), rel=1e-14)
+        assert z[3, 2 * p + 1] == pytest.approx(r * math.sin(theta), rel=1e-14)
+    np.testing.assert_allclose(z[3], [-1.1119912759619732, -0.41324689662142744,
+                                      -0.567765032350208, -0.4887853427327387], rtol=1e-14)
+    # the draws are those of the row index, whatever n is
+    np.testing.assert_array_equal(cref.policy_noise_np(4, seed, counter)[0], z[:4])
+    # standard normal, the four columns uncorrelated (2^18 rows: 5 sigma = 0.01)
+    zz, _ = cref.policy_noise_np(1 << 18, 5, 17)
+    assert abs(zz.mean()) < 5e-3 and abs(zz.std() - 1) < 5e-3
+    assert np.abs(np.corrcoef(zz.T) - np.eye(4)).max() < 0.01
+
+
 def test_gae_known_answers():
     rng = np.random.default_rng(3)
     T, N = 17, 9

@@ -513,3 +513,509 @@ def test_deferred_finish_equals_separate_finishes(arch, m):
         assert (ga - gb).abs().max().item() <= 1e-5 * scale
     assert (pa - pb).abs().max().item() <= 1e-5
     assert torch.equal(pb, pc) and all(torch.equal(x[0], y[0]) for x, y in zip(b, c))
+
+
+# ------------------------------------------------- dr_ppo_loss rows against f64
+U = 2.0 ** -24          # fp32 unit roundoff; one ulp is at most 2 U relative
+LOG_SQRT_2PI = 0.5 * np.log(2 * np.pi)
+
+
+def _adv_stats_bound(adv32):
+    """Error bounds of dr_ppo_loss's advantage statistics (adv_stats_kernel's
+    per-block (count, mean, M2), merged in double by Chan's formula), from
+    the f32 inputs alone: (|d mean|, relative |d std|).
+
+    Block b (<= 256 rows): its sum is a tree of depth 9 (6 wave shuffles, 3
+    adds across the 4 waves), |d sum| <= gamma_9 sum|a|, and the division by
+    the count is one more operation (<= 1 ulp = 2 U), so the block mean is off
+    by |eps_b| <= e_b = (gamma_9 + 2 U) mean_b|a|.  The merged mean is the
+    count-weighted mean of the block means (double: exact here), off by at
+    most ebar = sum_b n_b e_b / N, plus its rounding to f32.
+
+    M2.  The block's M2 is taken about its COMPUTED mean: sum (a_i - m_b -
+    eps_b)^2 = M2_b + n_b eps_b^2 exactly (the first-order term vanishes,
+    sum (a_i - m_b) = 0), and Chan's merge adds n_b (m_b + eps_b - mu -
+    epsbar)^2.  A block-mean error common to all blocks cancels in eps_b -
+    epsbar, so it enters at second order only; the blocks' differing errors
+    enter as 2 n_b (m_b - mu)(eps_b - epsbar), first order but scaled by the
+    block means' spread (sigma / 16 for 256-row blocks).  Hence
+      |d M2| <= sum_b n_b [2 |m_b - mu| (e_b + ebar) + (e_b + ebar)^2 + e_b^2]
+                + gamma_13 M2
+    (gamma_13: each fl(a_i - m_b)^2 carries 3 roundings, the tree 9, the f32
+    partial 1).  std = sqrtf(M2 / (N - 1)): the f32 rounding of M2, the
+    division and the square root (<= 1 ulp each) add 0.5 (U + 2 U) + 2 U."""
+    a = np.asarray(adv32, np.float64)
+    N = len(a)
+    mu = a.mean()
+    M2 = ((a - mu) ** 2).sum()
+    g9, g13 = 9 * U / (1 - 9 * U), 13 * U / (1 - 13 * U)
+    nb, mb, eb = [], [], []
+    for s in range(0, N, 256):
+        blk = a[s:s + 256]
+        nb.append(len(blk))
+        mb.append(blk.mean())
+        eb.append((g9 + 2 * U) * np.abs(blk).mean())
+    nb, mb, eb = map(np.array, (nb, mb, eb))
+    ebar = (nb * eb).sum() / N
+    d_mu = ebar + U * abs(mu)
+    d_m2 = (nb * (2 * np.abs(mb - mu) * (eb + ebar) + (eb + ebar) ** 2 + eb ** 2)).sum() + g13 * M2
+    return d_mu, 0.5 * (d_m2 / M2 + 3 * U) + 2 * U
+
+
+def _loss_rows_f64(mean, log_std, values, act, old_logp, adv, ret, clip, ent, vf, normalize):
+    """torch f64 autograd of SB3's minibatch loss w.r.t. (mean, log_std,
+    values), and the per-row quantities the bounds are built from."""
+    t = lambda x: torch.as_tensor(x).double()      # noqa: E731
+    mu = t(mean).clone().requires_grad_(True)
+    ls = t(log_std).clone().requires_grad_(True)
+    v = t(values).clone().requires_grad_(True)
+    a, olp, A_raw, R = t(act), t(old_logp), t(adv), t(ret)
+    m = mu.shape[0]
+    z = (a - mu) / ls.exp()
+    lp = (-0.5 * z ** 2 - ls - LOG_SQRT_2PI).sum(1)
+    A = (A_raw - A_raw.mean()) / (A_raw.std() + 1e-8) if (normalize and m > 1) else A_raw
+    logr = lp - olp
+    r = logr.exp()
+    surr = torch.min(A * r, A * r.clamp(1 - clip, 1 + clip))
+    H = (0.5 + LOG_SQRT_2PI + ls).sum()
+    verr = (R - v) ** 2
+    loss = -surr.mean() - ent * H + vf * verr.mean()
+    loss.backward()
+    with torch.no_grad():
+        kl = (r - 1) - logr
+        return dict(g_mean=mu.grad.numpy(), g_ls=ls.grad.numpy(), g_v=v.grad.numpy(),
+                    z=z.numpy(), q=(0.5 * z ** 2).numpy(), A=A.numpy(), A_raw=A_raw.numpy(),
+                    r=r.numpy(), logr=logr.numpy(), surr=surr.numpy(), verr=verr.numpy(),
+                    kl=kl.numpy(), H=H.item(), sd=ls.exp().detach().numpy(),
+                    ls=ls.detach().numpy(),
+                    clip_count=int(((r - 1).abs() > clip).sum()),
+                    stats=[loss.item(), -surr.mean().item(), verr.mean().item(), -H.item(),
+                           ((r - 1).abs() > clip).double().mean().item(), kl.mean().item()])
+
+
+def _loss_row_bounds(ref, m, clip, ent, vf, normalize):
+    """fp32 error bounds of dr_ppo_loss's outputs from ppo_row's operation
+    chain (U = 2^-24; a correctly rounded operation costs U relative, a
+    device-library function -- expf, logf, sqrtf, the reciprocals -- <= 1 ulp
+    = 2 U; -ffp-contract=off: every product and sum is rounded separately):
+
+      sd = expf(ls) 2U; var = sd sd 5U; inv_var, inv_2var 7U
+      d = a - mu U; zz = d inv_var 9U; q = (d d) inv_2var 11U; y = (d d) inv_var 11U
+      logsd = logf(sd): 2U |ls| + 2U absolute (the 2U of sd moves the log by 2U)
+      lp: 4 x (q - logsd - c): E_lp = 11 sum q + 2 sum(|ls| + 1) + 4 c  (terms)
+                                     + 12 S, S = sum(q + |ls| + c)       (12 adds)
+      logr = lp - old: d_logr = U (E_lp + |logr|) absolute
+      r = expf(logr): rho_r = d_logr + 2U relative
+      A = (A - mean) inv_astd: d_A = (U |A - mean| + d_mean) / std
+                                     + |A| (rho_std + 4U)   (_adv_stats_bound;
+                                     inv_astd = 1 / (std + 1e-8): 3U, product U)
+      dr = -(..A..) inv_m: the branch weights are exact (0, 1/2, 1; a tie is
+           A/2 + A/2), inv_m 2U, product U;  dlp = dr r: + rho_r + U
+      g_mean_j = dlp zz_j: |g| (rho_r + 14U) + (r |zz_j| / m) d_A
+      g_value = vf (2 (v - R)) inv_m: 6U relative
+      g_log_std_j = sum_i t_i - ent, t = dlp (y - 1):
+           sum_i [|t| (rho_r + 5U) + (r |y - 1| / m) d_A + |dlp| (11U y + U |y - 1|)]
+           + gamma_m sum|t| (a sum of m terms in any grouping) + U |result|
+      policy_loss = sum(-min(A r, A rc)) inv_m, rc = r or 1 -+ clip (<= 2U):
+           mean[|l| (rho_r + 3U) + r d_A] + (gamma_m + 3U) mean|l|
+      value_loss = sum((R - v)^2) inv_m: (gamma_m + 6U) relative (positive terms)
+      approx_kl = sum((r - 1) - logr) inv_m:
+           mean[r rho_r + U |r - 1| + d_logr + U |t|] + (gamma_m + 3U) mean|t|
+      entropy_loss = -sum_j(0.5 + c + ls_j): 12 adds of partial sums <= E_H =
+           sum(0.5 + c + |ls_j|): 12U E_H + 4U c
+      loss = pl + ent el + vf vl: the three bounds + 4U (|pl| + |ent el| + |vf vl|)
+    """
+    gm = lambda n: n * U / (1 - n * U)             # noqa: E731
+    q, ls, r, A = ref["q"], ref["ls"], ref["r"], ref["A"]
+    S = (q + np.abs(ls) + LOG_SQRT_2PI).sum(1)
+    E_lp = 11 * q.sum(1) + 2 * (np.abs(ls) + 1).sum() + 4 * LOG_SQRT_2PI + 12 * S
+    d_logr = U * (E_lp + np.abs(ref["logr"]))
+    rho_r = d_logr + 2 * U
+    if normalize and m > 1:
+        d_mu, rho_sd = _adv_stats_bound(ref["A_raw"].astype(np.float32))
+        std = ref["A_raw"].std(ddof=1)
+        d_A = (U * np.abs(ref["A_raw"] - ref["A_raw"].mean()) + d_mu) / std + \
+            np.abs(A) * (rho_sd + 4 * U)
+    else:
+        d_A = np.zeros(m)
+    zz = np.abs(ref["z"]) / ref["sd"]
+    b = {}
+    b["g_mean"] = np.abs(ref["g_mean"]) * (rho_r + 14 * U)[:, None] + \
+        (r[:, None] * zz / m) * d_A[:, None]
+    b["g_v"] = 6 * U * np.abs(ref["g_v"])
+    y = 2 * q
+    # |dlp| = |A| r / m on the rows whose unclipped branch carries the gradient;
+    # bounding every row by it only loosens the bound where the gradient is 0
+    dlp = (np.abs(A) * r / m)[:, None]
+    t = dlp * np.abs(y - 1)
+    b["g_ls"] = (t * (rho_r + 5 * U)[:, None] + (r[:, None] * np.abs(y - 1) / m) * d_A[:, None] +
+                 dlp * (11 * U * y + U * np.abs(y - 1))).sum(0) + gm(m) * t.sum(0) + \
+        U * np.abs(ref["g_ls"])
+    l = np.abs(ref["surr"])
+    pl = (l * (rho_r + 3 * U) + np.maximum(r, 1 + clip) * d_A).mean() + (gm(m) + 3 * U) * l.mean()
+    vl = (gm(m) + 6 * U) * ref["verr"].mean()
+    kl = (r * rho_r + U * np.abs(r - 1) + d_logr + U * np.abs(ref["kl"])).mean() + \
+        (gm(m) + 3 * U) * np.abs(ref["kl"]).mean()
+    E_H = (0.5 + LOG_SQRT_2PI + np.abs(ls)).sum()
+    el = 12 * U * E_H + 4 * U * LOG_SQRT_2PI
+    st = ref["stats"]
+    tot = pl + abs(ent) * el + vf * vl + 4 * U * (abs(st[1]) + abs(ent * st[3]) + abs(vf * st[2]))
+    b["stats"] = [tot, pl, vl, el, 0.0, kl]
+    return b
+
+
+def _loss_inputs(m):
+    """PPOLoss inputs on the in-distribution fixture: the f64 forward's mean
+    and values rounded to f32."""
+    from ppo_f64 import midtraining_minibatch
+    mb = midtraining_minibatch(15, (64, 64), m, seed=3)
+    return dict(mean=mb["mean64"].float().numpy(), log_std=mb["sd"]["log_std"].numpy(),
+                values=mb["value64"].float().numpy(), act=mb["act"].numpy(),
+                old_logp=mb["old_logp"].numpy(), adv=mb["adv"].numpy(), ret=mb["ret"].numpy())
+
+
+def _run_loss(x, m, clip, ent, vf, normalize):
+    from drone_rl_amd import ppo_kernels as K
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    L = K.PPOLoss(m, "cuda", clip, ent, vf, normalize)
+    gm, gls, gv, st = L(cu(x["mean"]), cu(x["log_std"]), cu(x["values"]), cu(x["act"]),
+                        cu(x["old_logp"]), cu(x["adv"]), cu(x["ret"]))
+    torch.cuda.synchronize()
+    return (gm.cpu().numpy().astype(np.float64), gls.cpu().numpy().astype(np.float64),
+            gv.cpu().numpy().astype(np.float64), st.cpu().numpy().astype(np.float64))
+
+
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("m", [1, 255, 257, 4099])
+def test_ppo_loss_rows_match_f64_entrywise(m, normalize):
+    """dr_ppo_loss on a minibatch that engages the clip, at one row, one block
+    less one row, one block plus one row and 17 blocks: grad_mean and
+    grad_values entrywise, grad_log_std and the stats, against torch f64
+    autograd of the same expression, within the bounds of ppo_row's operation
+    chain (_loss_row_bounds, _adv_stats_bound: the derivation).  The
+    clip count is exact.  At m = 1 normalize_advantage changes nothing (SB3
+    normalises only when len(advantages) > 1).
+    Measured on an MI355X, worst error / bound over the eight cases:
+    grad_mean 0.128, grad_values 0.467, grad_log_std 0.075, loss 0.056,
+    policy_loss 0.064, value_loss 0.179, entropy_loss 0.013, approx_kl 0.001
+    (the sums' worst cases at m = 1, where the bound has no slack from
+    rounding errors cancelling across rows)."""
+    clip, ent, vf = 0.2, 0.01, 0.5
+    x = _loss_inputs(m)
+    ref = _loss_rows_f64(x["mean"], x["log_std"], x["values"], x["act"], x["old_logp"],
+                         x["adv"], x["ret"], clip, ent, vf, normalize)
+    b = _loss_row_bounds(ref, m, clip, ent, vf, normalize)
+    gm, gls, gv, st = _run_loss(x, m, clip, ent, vf, normalize)
+    tiny = 1e-37                       # below the smallest normal f32: underflow
+    ratios = {
+        "grad_mean": (np.abs(gm - ref["g_mean"]) / (b["g_mean"] + tiny)).max(),
+        "grad_values": (np.abs(gv - ref["g_v"]) / (b["g_v"] + tiny)).max(),
+        "grad_log_std": (np.abs(gls - ref["g_ls"]) / (b["g_ls"] + tiny)).max(),
+    }
+    for i, name in ((0, "loss"), (1, "policy_loss"), (2, "value_loss"), (3, "entropy_loss"),
+                    (5, "approx_kl")):
+        ratios[name] = abs(st[i] - ref["stats"][i]) / (b["stats"][i] + tiny)
+    print(f"m {m} normalize {normalize}: " +
+          ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()) +
+          f"; clip count {round(st[4] * m)} / {ref['clip_count']}")
+    for k, v in ratios.items():
+        assert v <= 1.0, f"{k}: error {v:.3f} x its fp32 bound"
+    assert round(st[4] * m) == ref["clip_count"]
+    assert abs(st[4] - ref["clip_count"] / m) <= 3 * U * ref["clip_count"] / m
+    if m > 1:
+        assert 0.2 * m <= ref["clip_count"] <= 0.7 * m
+    if not normalize:
+        assert st[6] == 0.0 and st[7] == 1.0
+    if m == 1 and normalize:
+        raw = _run_loss(x, m, clip, ent, vf, False)
+        for u, v in zip((gm, gls, gv, st), raw):
+            assert np.array_equal(u, v)
+
+
+@pytest.mark.parametrize("offset", [0.0, 100.0, 1e4])
+@pytest.mark.parametrize("m", [257, 4099])
+def test_ppo_loss_advantage_statistics_match_f64(m, offset):
+    """stats[6] / stats[7] (the minibatch advantage mean and unbiased std the
+    normalisation uses) against the f64 mean and std of the same f32 inputs,
+    unit spread around 0, 100 and 10,000 -- where a one-pass sum of squares
+    would lose the variance -- within _adv_stats_bound (the derivation).
+    Measured on an MI355X, worst error / bound (mean, std):
+    0.105, 0.059 (bounds at m = 4099: |d mean| 5.2e-7 / 7.2e-5 / 7.2e-3 and
+    relative |d std| 6.5e-7 / 8.0e-6 / 8.5e-4 at offsets 0 / 100 / 10,000)."""
+    x = _loss_inputs(m)
+    g = torch.Generator().manual_seed(m)
+    x["adv"] = (offset + torch.randn(m, generator=g, dtype=torch.float64)).float().numpy()
+    _, _, _, st = _run_loss(x, m, 0.2, 0.0, 0.5, True)
+    a = x["adv"].astype(np.float64)
+    d_mu, rho_sd = _adv_stats_bound(x["adv"])
+    r_mu = abs(st[6] - a.mean()) / d_mu
+    r_sd = abs(st[7] - a.std(ddof=1)) / (rho_sd * a.std(ddof=1))
+    print(f"m {m} offset {offset:g}: mean error / bound {r_mu:.3f} (bound {d_mu:.3g}), "
+          f"std error / bound {r_sd:.3f} (relative bound {rho_sd:.3g})")
+    assert r_mu <= 1.0 and r_sd <= 1.0
+
+
+# --------------------------------------------- policy_sample against the oracle
+SAMPLE_SEED, SAMPLE_COUNTER = 0x1234567890, (7 << 32) + 5
+LO, HI = 0.0, 7.3575
+
+
+def _sample(n, mean, log_std, seed=SAMPLE_SEED, counter=SAMPLE_COUNTER, want=(1, 1, 1),
+            dev=None):
+    from drone_rl_amd import ppo_kernels as K
+    raw = torch.full((n, 4), float("nan"), device="cuda") if want[0] else None
+    clip = torch.full((n, 4), float("nan"), device="cuda") if want[1] else None
+    logp = torch.full((n,), float("nan"), device="cuda") if want[2] else None
+    if dev is None:
+        K.policy_sample(mean, log_std, seed, counter, LO, HI, raw, clip, logp)
+    else:
+        base = torch.tensor([dev[0]], dtype=torch.int64, device="cuda")
+        K.policy_sample_dev(mean, log_std, seed, base, dev[1], LO, HI, raw, clip, logp)
+    torch.cuda.synchronize()
+    return raw, clip, logp
+
+
+@pytest.mark.parametrize("log_std", [[0.0, -0.5, 0.3, -1.0], [-5.0, -1.0, 0.0, 2.0]])
+@pytest.mark.parametrize("n", [1, 255, 257, 4099])
+def test_policy_sample_matches_philox_oracle(n, log_std):
+    """dr_policy_sample per element against oracle/cref.policy_noise_np, with
+    both high words of the seed and of the counter live.
+
+    Noise.  z = r cos(theta) (or sin), r = sqrtf(-2 logf(u1)); u1, u2 and
+    theta are formed exactly as the oracle forms them.  With the device
+    library's documented bounds (logf, sqrtf, sincosf, expf: <= 1 ulp =
+    2^-23 relative each; the HIP math API's table -- not available on the
+    build machine, so taken as stated there): logf's 2^-23 is halved by the
+    square root, sqrtf adds 2^-23, cos / sin 2^-23, the product 2^-24:
+    |dz| <= 3 * 2^-23 r (|cos|, |sin| <= 1).  The test reads z back as
+    (raw - mean) / exp(log_std) in f64: raw = fl(mean + fl(sd z)) adds 2^-24
+    |z| + 2^-24 |raw| / sd, and sd = expf(log_std) (<= 1 ulp) 2^-23 |z|; the
+    f64 subtraction and division add 2^-52 (|raw| + |mean|) / sd.
+    Log-prob, from the kernel's own raw, against f64: four terms -(d d)
+    inv_2var - logf(sd) - c; q = (d d) inv_2var carries 11 roundings (d 1, d d
+    2 + 1, inv_2var 2 x 2 + 1 + 2, product 1), logf(sd) 2^-23 (|ls| + 1), the
+    constant 2^-24 c, and the 12 additions 2^-24 S each, S = sum(q + |ls| + c):
+    |d logp| <= 2^-24 (11 sum q + 2 sum(|ls| + 1) + 4 c + 12 S).
+    Clipped actions: clamp(raw, lo, hi) exactly.
+    Measured on an MI355X, worst error / bound (noise, log-prob):
+    0.970, 0.126.  Against 3 * 2^-23 r alone the read-back noise is off by up
+    to 43 x (log_std >= -1) and 1,490 x (log_std = -5): that is the rounding
+    of mean + sd z divided by sd, which the bound carries, not the draw."""
+    g = torch.Generator().manual_seed(n)
+    mean = (2.0 + 2.0 * torch.randn(n, 4, generator=g)).cuda()
+    ls = torch.tensor(log_std, device="cuda")
+    raw, clip, logp = _sample(n, mean, ls)
+    z_ref, rad = cref.policy_noise_np(n, SAMPLE_SEED, SAMPLE_COUNTER)
+    mu = mean.cpu().numpy().astype(np.float64)
+    a = raw.cpu().numpy().astype(np.float64)
+    lsd = np.array(log_std, np.float32).astype(np.float64)
+    sd = np.exp(lsd)
+    z = (a - mu) / sd
+    tol = 3 * 2.0 ** -23 * rad + (2.0 ** -23 + 2.0 ** -24) * np.abs(z_ref) + \
+        2.0 ** -24 * np.abs(a) / sd + 2.0 ** -52 * (np.abs(a) + np.abs(mu)) / sd
+    r_z = (np.abs(z - z_ref) / tol).max()
+    # the share of the bound that is the draw's own (c 2^-23 r), for the record
+    r_draw = (np.abs(z - z_ref) / (3 * 2.0 ** -23 * rad + 1e-300)).max()
+    q = 0.5 * z ** 2
+    lp_ref = (-q - lsd - LOG_SQRT_2PI).sum(1)
+    S = (q + np.abs(lsd) + LOG_SQRT_2PI).sum(1)
+    lp_tol = U * (11 * q.sum(1) + 2 * (np.abs(lsd) + 1).sum() + 4 * LOG_SQRT_2PI + 12 * S)
+    r_lp = (np.abs(logp.cpu().numpy().astype(np.float64) - lp_ref) / lp_tol).max()
+    print(f"n {n} log_std {log_std}: noise error / bound {r_z:.3f} "
+          f"(against 3 * 2^-23 r alone: {r_draw:.3f}), log-prob error / bound {r_lp:.3f}")
+    assert r_z <= 1.0 and r_lp <= 1.0
+    assert torch.equal(clip, raw.clamp(LO, HI))
+    if n == 4099:                      # both ends of the clamp are engaged
+        assert (raw < LO).any() and (raw > HI).any()
+
+
+def test_policy_sample_device_counter_optional_outputs_and_streams():
+    """dr_policy_sample_dev reads counter_base + counter_offset on the device:
+    bitwise dr_policy_sample at the sum, with a carry from the low word into
+    the high one.  Any subset of the three outputs may be null and the others
+    keep their bytes.  The high seed word, the high counter word and the row
+    index each select a different stream."""
+    n = 4099
+    g = torch.Generator().manual_seed(7)
+    mean = torch.randn(n, 4, generator=g).cuda()
+    ls = torch.tensor([0.0, -0.5, 0.3, -1.0], device="cuda")
+    full = _sample(n, mean, ls)
+    # device counter, no carry and a carry out of the low word
+    for c0, c1 in (((7 << 32), 5), ((6 << 32) + 0xfffffffe, 7), (5, (7 << 32))):
+        assert c0 + c1 == SAMPLE_COUNTER
+        got = _sample(n, mean, ls, dev=(c0, c1))
+        for u, v in zip(full, got):
+            assert torch.equal(u, v), (c0, c1)
+    # optional outputs
+    for want in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (0, 0, 0)):
+        for dev in (None, ((6 << 32) + 0xfffffffe, 7)):
+            got = _sample(n, mean, ls, want=want, dev=dev)
+            for w, u, v in zip(want, full, got):
+                assert (v is None) if not w else torch.equal(u, v), (want, dev)
+    # stream separation: only the high seed word / only the high counter word
+    raw = full[0]
+    for seed, counter in ((SAMPLE_SEED ^ (1 << 36), SAMPLE_COUNTER),
+                          (SAMPLE_SEED, SAMPLE_COUNTER ^ (1 << 35)),
+                          (SAMPLE_SEED ^ 1, SAMPLE_COUNTER), (SAMPLE_SEED, SAMPLE_COUNTER ^ 1)):
+        other = _sample(n, mean, ls, seed=seed, counter=counter, want=(1, 0, 0))[0]
+        assert (other != raw).float().mean().item() > 0.99, (hex(seed), hex(counter))
+    # only i: rows with the same mean draw different noise, and the four
+    # dimensions of a row are four different draws
+    same = _sample(n, torch.zeros(n, 4, device="cuda"), torch.zeros(4, device="cuda"),
+                   want=(1, 0, 0))[0].cpu().numpy()
+    assert len(np.unique(same, axis=0)) == n
+    assert len(np.unique(same.ravel())) > 0.999 * 4 * n
+    c = np.corrcoef(same.T)
+    assert np.abs(c - np.eye(4)).max() < 5 / np.sqrt(n)
+
+
+# ------------------------------------- small shapes and loops no test had reached
+@pytest.mark.parametrize("T,N", [(1, 1), (1, 257), (5, 255), (33, 256), (7, 1000)])
+def test_gae_bitexact_small_shapes_and_edges(T, N):
+    """dr_gae == the C oracle bit for bit at one env, one step, ragged and
+    whole blocks; episode_starts all zero, all one and random; last_dones
+    random and all one; the default (gamma, lambda), (1, 1) and lambda = 0."""
+    from drone_rl_amd import ppo_kernels as K
+    rng = np.random.default_rng(T * 1000 + N)
+    r = rng.normal(size=(T, N)).astype(np.float32)
+    v = rng.normal(size=(T, N)).astype(np.float32)
+    lv = rng.normal(size=N).astype(np.float32)
+    cu = lambda x: torch.from_numpy(x).cuda()  # noqa: E731
+    starts = {"zero": np.zeros((T, N), np.uint8), "one": np.ones((T, N), np.uint8),
+              "random": (rng.random((T, N)) < 0.3).astype(np.uint8)}
+    dones = {"random": (rng.random(N) < 0.3).astype(np.uint8), "one": np.ones(N, np.uint8)}
+    for sname, st in starts.items():
+        for dname, ld in dones.items():
+            for gamma, lam in ((0.99, 0.95), (1.0, 1.0), (0.9, 0.0)):
+                adv, ret = K.gae(cu(r), cu(v), cu(st), cu(lv), cu(ld), gamma, lam)
+                ra, rr = cref.gae(r, v, st, lv, ld, gamma, lam)
+                what = f"starts {sname}, last_dones {dname}, gamma {gamma}, lambda {lam}"
+                np.testing.assert_array_equal(adv.cpu().numpy(), ra, err_msg=what)
+                np.testing.assert_array_equal(ret.cpu().numpy(), rr, err_msg=what)
+
+
+def _clip_adam_f64(p, g, m, v, step, lr=3e-4, b1=0.9, b2=0.999, eps=1e-5, max_norm=0.5):
+    """clip_grad_norm_ + torch.optim.Adam (oracle/ppo_ref.clip_adam_torch's
+    math) restated in f64: (params, exp_avg, exp_avg_sq, clipped grad, norm)."""
+    p, g, m, v = (np.asarray(x, np.float64) for x in (p, g, m, v))
+    norm = np.sqrt((g * g).sum())
+    c = min(1.0, max_norm / (norm + 1e-6))
+    gc = g * c
+    m1 = m + (1 - b1) * (gc - m)
+    v1 = b2 * v + (1 - b2) * gc * gc
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    p1 = p - (lr / bc1) * (m1 / (np.sqrt(v1) / np.sqrt(bc2) + eps))
+    return p1, m1, v1, gc, norm
+
+
+def _close_to_f64(opt, gd, p0, ref):
+    """test_clip_adam_vs_torch's element tolerances.  They cover the fp32
+    rounding of the ten or so elementwise operations of clip + Adam (each
+    2^-24 relative: 1e-5 leaves a factor ten) and the norm's reduction order
+    in the clip factor; the floor relative to each array's largest entry
+    covers entries that cancel (exp_avg + w (g - exp_avg) near zero).  The
+    update is read back as p_new - p_old, and p_new = fl(p_old - step) is
+    itself rounded to f32: 2^-24 |p_new| more, which at 141,065 elements hides
+    below the floor (some update is always large) and at a few hundred
+    elements does not."""
+    rp, rm, rv, rg, rnorm = ref
+    norm = opt.grad_norm.item()
+    assert abs(norm - rnorm) <= 1e-5 * rnorm
+
+    def close(a, b, rel):
+        np.testing.assert_allclose(a, b, rtol=rel, atol=rel * np.abs(b).max())
+    close(gd.cpu().numpy(), rg, 1e-5)
+    close(opt.m.cpu().numpy(), rm, 1e-5)
+    close(opt.v.cpu().numpy(), rv, 1e-5)
+    upd, rupd = opt.p.cpu().numpy().astype(np.float64) - p0, rp - p0
+    assert (np.abs(upd - rupd) <= 1e-4 * np.abs(rupd) + 1e-4 * np.abs(rupd).max() +
+            2.0 ** -24 * np.abs(rp)).all()
+    np.testing.assert_allclose(opt.p.cpu().numpy(), rp, rtol=1e-6, atol=1e-7)
+
+
+def _adam_state(n, gscale, seed):
+    rng = np.random.default_rng(seed)
+    p = rng.normal(size=n).astype(np.float32)
+    g = (rng.normal(size=n) * gscale / np.sqrt(n)).astype(np.float32)
+    m = (rng.normal(size=n) * 1e-3).astype(np.float32)
+    v = (rng.random(n) * 1e-6).astype(np.float32)
+    return p, g, m, v
+
+
+def _adam_opt(p, m, v, step):
+    from drone_rl_amd import ppo_kernels as K
+    opt = K.ClipAdam(torch.from_numpy(p.copy()).cuda())
+    opt.m.copy_(torch.from_numpy(m))
+    opt.v.copy_(torch.from_numpy(v))
+    opt.t = step - 1
+    return opt
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 2048 * 256 + 257])
+def test_clip_adam_matches_f64_at_small_sizes_and_in_the_grid_stride_loops(n):
+    """dr_clip_adam against the f64 restatement at one element, a ragged
+    block, a block plus one, and 2048 x 256 + 257 elements -- above the
+    2048-block cap of the launch, so sumsq_kernel's and clip_adam_kernel's
+    grid-stride loops run a second trip (for 257 elements only); clipped and
+    unclipped gradients; an all-zero gradient (norm 0, nothing NaN, Adam's
+    update from the old moments)."""
+    for gscale, step in ((10.0, 1), (1e-4, 7), (0.0, 3)):
+        p, g, m, v = _adam_state(n, gscale, n + step)
+        opt = _adam_opt(p, m, v, step)
+        gd = torch.from_numpy(g.copy()).cuda()
+        opt.step(gd)
+        torch.cuda.synchronize()
+        if gscale == 0.0:
+            assert opt.grad_norm.item() == 0.0
+            assert torch.equal(gd, torch.zeros_like(gd))
+            for t in (opt.p, opt.m, opt.v):
+                assert torch.isfinite(t).all()
+            rp, rm, rv, _, _ = _clip_adam_f64(p, g, m, v, step)
+            np.testing.assert_allclose(opt.m.cpu().numpy(), rm, rtol=1e-6)
+            np.testing.assert_allclose(opt.v.cpu().numpy(), rv, rtol=1e-6)
+            upd = opt.p.cpu().numpy().astype(np.float64) - p
+            assert (np.abs(upd - (rp - p)) <= 1e-4 * np.abs(rp - p) +
+                    1e-4 * np.abs(rp - p).max() + 2.0 ** -24 * np.abs(rp)).all()
+            continue
+        _close_to_f64(opt, gd, p, _clip_adam_f64(p, g, m, v, step))
+        # (an element the loops skipped, or visited twice, misses the update
+        # tolerance above: its error is the whole update)
+        if n > 1000:
+            assert (opt.p.cpu().numpy() != p).mean() > 0.99
+
+
+@pytest.mark.parametrize("n", [257, 2048 * 256 + 257])
+def test_clip_adam_sched_and_grad_scale(n):
+    """dr_clip_adam_sched (the data-parallel step's optimizer): with
+    grad_scale 1 bitwise dr_clip_adam of the same step count; with grad_scale
+    0.5 bitwise dr_clip_adam of 0.5 g (a power of two is exact through the
+    norm and the clip); with grad_scale 1/3 within the element tolerances of
+    the f64 restatement on g / 3."""
+    step = 4
+    for gscale in (10.0, 1e-4):
+        p, g, m, v = _adam_state(n, gscale, n + 11)
+
+        def run(grad, scale):
+            opt = _adam_opt(p, m, v, step)
+            gd = torch.from_numpy(grad.copy()).cuda()
+            if scale is None:
+                opt.step(gd)
+            else:
+                sched = opt.schedule(step, 1)[0].contiguous().cuda()
+                opt.step_sched(gd, sched, scale)
+            torch.cuda.synchronize()
+            return opt, gd
+
+        base, gb = run(g, None)
+        one, g1 = run(g, 1.0)
+        for a, b in ((base.p, one.p), (base.m, one.m), (base.v, one.v), (gb, g1),
+                     (base.grad_norm, one.grad_norm)):
+            assert torch.equal(a, b)
+        half_ref, gh = run((0.5 * g).astype(np.float32), None)
+        half, g2 = run(g, 0.5)
+        for a, b in ((half_ref.p, half.p), (half_ref.m, half.m), (half_ref.v, half.v),
+                     (gh, g2), (half_ref.grad_norm, half.grad_norm)):
+            assert torch.equal(a, b)
+        assert not torch.equal(half.p, base.p)
+        third, g3 = run(g, 1.0 / 3.0)
+        _close_to_f64(third, g3, p, _clip_adam_f64(p, g.astype(np.float64) / 3.0, m, v, step))
