@@ -28,6 +28,7 @@ DR_VARIANT_GYM = 0
 DR_VARIANT_VECTORIZED = 1
 DR_VARIANT_MOVING = 2
 DR_VARIANT_SMOOTH = 3
+DR_VARIANT_TAG = 4
 DR_STATE_F64 = 0
 DR_STATE_F32 = 1
 DR_RNG_PHILOX = 0
@@ -89,6 +90,8 @@ SIGNATURES = {
     "dr_set_seed": (c_int, [_P, c_uint64]),
     "dr_set_smoothing": (c_int, [_P, c_float, c_float]),
     "dr_get_smoothing": (c_int, [_P, _P, _P]),
+    "dr_set_tag": (c_int, [_P, c_float, c_float]),
+    "dr_get_tag": (c_int, [_P, _P, _P]),
     "dr_rollout": (c_int, [_P, c_int32, _P, _P, _P, _P, _P]),
     "dr_rollout_timed": (c_int, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "dr_rollout_random": (c_int, [_P, c_int32, c_uint64, c_int64, c_float, c_float, _P, _P,

@@ -8,7 +8,9 @@
 // (N,15) f32 observation rows (60 B, not 16 B aligned per env) are staged
 // through LDS and leave the block as contiguous float4 stores.  The moving
 // variant adds 9 f32 motion arrays and 3 obs floats, the smooth variant 4 f32
-// motor-force arrays and 4 obs floats (DESIGN.md sections 11 and 14).
+// motor-force arrays and 4 obs floats (DESIGN.md sections 11 and 14).  The tag
+// variant couples env 2j with env 2j+1 through in-register lane exchanges; its
+// obs has 19 floats and it keeps no state of its own.
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -429,11 +431,14 @@ __device__ inline void moving_reset_regs(const EnvView<S> &v, int64_t i, int mod
 // Observation width of a variant.
 template <int VAR>
 constexpr int od_of() {
-    return VAR == DR_VARIANT_GYM ? 15
-                                 : (VAR == DR_VARIANT_MOVING ? 18 : (VAR == DR_VARIANT_SMOOTH ? 19 : 12));
+    return VAR == DR_VARIANT_GYM
+               ? 15
+               : (VAR == DR_VARIANT_MOVING
+                      ? 18
+                      : ((VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG) ? 19 : 12));
 }
 // What a variant's kernels take beyond the shared arguments: nothing, or the
-// smooth variant's two parameters.  A trailing kernel argument of its own, so
+// smooth / tag variant's two parameters.  A trailing kernel argument of its own, so
 // the argument blocks of the other variants' kernels stay as they were.
 template <int VAR>
 struct VarArgs {};
@@ -441,6 +446,11 @@ template <>
 struct VarArgs<DR_VARIANT_SMOOTH> {
     float alpha;   // lag blend dt / (tau + dt), in (0, 1]
     float lam;     // action-rate penalty, >= 0
+};
+template <>
+struct VarArgs<DR_VARIANT_TAG> {
+    float radius;  // tag radius R > 0
+    float crash;   // crash penalty c >= 0
 };
 // the force every motor applies after a reset: f32(mass * g / 4)
 constexpr float kHover32 = (float)(kMass * kG / 4);
@@ -461,23 +471,87 @@ __device__ inline float4 smooth_filter(float4 a, float f[4], float alpha, float 
     return make_float4(f[0], f[1], f[2], f[3]);
 }
 
+// ---- tag variant (DR_VARIANT_TAG) ----
+// Envs 2j (pursuer) and 2j+1 (evader) sit in lanes l and l^1 of one wave.
+// The partner's value of a register: a lane <-> lane^1 swap that touches no
+// memory.  It must execute with all 64 lanes of the wave active (a lane
+// reads what its partner holds, and an inactive partner supplies nothing),
+// so it is only ever called from wave-uniform code.
+// DR_TAG_XCHG 0: DPP quad_perm:[1,0,3,2], one v_mov_b32_dpp per dword;
+// 1 (A/B builds): __shfl_xor(., 1), a ds_bpermute_b32 per dword.
+#ifndef DR_TAG_XCHG
+#define DR_TAG_XCHG 0
+#endif
+__device__ inline int partner_of(int x) {
+#if DR_TAG_XCHG
+    return __shfl_xor(x, 1);
+#else
+    // quad_perm [1,0,3,2] = 1 | 0 << 2 | 3 << 4 | 2 << 6
+    return __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);
+#endif
+}
+__device__ inline float partner_of(float x) {
+    return __int_as_float(partner_of(__float_as_int(x)));
+}
+__device__ inline double partner_of(double x) {
+    return __hiloint2double(partner_of(__double2hiint(x)), partner_of(__double2loint(x)));
+}
+// The partner's position and velocity (6 x S).
+template <typename S>
+__device__ inline void tag_partner(const S st[F_N], S pp[3], S pv[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        pp[k] = partner_of(st[F_POS + k]);
+        pv[k] = partner_of(st[F_VEL + k]);
+    }
+}
+// The obs past the gym's first 12: partner - own position and velocity
+// (S subtract, then the cast, as the gym's target - pos), then the role.
+template <typename S>
+__device__ inline void tag_ext(const S st[F_N], const S pp[3], const S pv[3], float sigma,
+                               float ext[7]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        ext[k] = (float)(pp[k] - st[F_POS + k]);
+        ext[3 + k] = (float)(pv[k] - st[F_VEL + k]);
+    }
+    ext[6] = sigma;
+}
+// The pursuer's reward g = 0.01 * (-d) [+ 1 inside R], the evader's -g, on
+// the new positions.  d is the same bit for bit in both lanes: the
+// differences are negatives of each other and the squares equal.
+template <typename S>
+__device__ inline S tag_reward(const S st[F_N], const S pp[3], float radius, bool pursuer) {
+    const S dx = st[F_POS + 0] - pp[0];
+    const S dy = st[F_POS + 1] - pp[1];
+    const S dz = st[F_POS + 2] - pp[2];
+    const S d = m_sqrt((dx * dx + dy * dy) + dz * dz);
+    S g = (S)0.01 * -d;
+    if (d < (S)radius) g += (S)1;
+    return pursuer ? g : -g;
+}
+
 // `ext`: the floats past the gym's 15 (moving: the target velocity, 3;
-// smooth: the motor forces, 4).
-template <typename S, int OD>
-__device__ inline void make_obs(const S st[F_N], float ob[OD],
+// smooth: the motor forces, 4); tag: the 7 floats past the first 12
+// (tag_ext).
+template <typename S, int VAR>
+__device__ inline void make_obs(const S st[F_N], float ob[od_of<VAR>()],
                                 const float *ext = nullptr) {
     // _get_obs: f32(concat(pos, vel, euler, omega[, target - pos]))  (79)
 #pragma unroll
     for (int k = 0; k < 12; ++k) ob[k] = (float)st[k];
-    if constexpr (OD >= 15) {
+    if constexpr (VAR == DR_VARIANT_TAG) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) ob[12 + k] = ext[k];
+    } else if constexpr (VAR != DR_VARIANT_VECTORIZED) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) ob[12 + k] = (float)(st[F_TGT + k] - st[F_POS + k]);
     }
-    if constexpr (OD == 18) {
+    if constexpr (VAR == DR_VARIANT_MOVING) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) ob[15 + k] = ext[k];
     }
-    if constexpr (OD == 19) {
+    if constexpr (VAR == DR_VARIANT_SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) ob[15 + k] = ext[k];
     }
@@ -554,17 +628,21 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     st[F_OMG + 2] += wd2 * dt;
 
     // Reward on the new position (142-148; vectorized_drone.py:204-207).
-    const S dx = st[F_POS + 0] - st[F_TGT + 0];
-    const S dy = st[F_POS + 1] - st[F_TGT + 1];
-    const S dz = st[F_POS + 2] - st[F_TGT + 2];
-    const S d = m_sqrt((dx * dx + dy * dy) + dz * dz);
-    S r;
-    if constexpr (VAR != DR_VARIANT_VECTORIZED) {
-        r = (S)0.01 * -d;
-        if (d < (S)0.05) r += (S)1;
-    } else {
-        r = (S)(-0.01) * d;
-        if (d < (S)1) r += (S)1;
+    // The tag variant's reward needs the partner's new position: the caller
+    // forms it (tag_reward) after the exchange.
+    S r = (S)0;
+    if constexpr (VAR != DR_VARIANT_TAG) {
+        const S dx = st[F_POS + 0] - st[F_TGT + 0];
+        const S dy = st[F_POS + 1] - st[F_TGT + 1];
+        const S dz = st[F_POS + 2] - st[F_TGT + 2];
+        const S d = m_sqrt((dx * dx + dy * dy) + dz * dz);
+        if constexpr (VAR != DR_VARIANT_VECTORIZED) {
+            r = (S)0.01 * -d;
+            if (d < (S)0.05) r += (S)1;
+        } else {
+            r = (S)(-0.01) * d;
+            if (d < (S)1) r += (S)1;
+        }
     }
     // Termination (154; vectorized_drone.py:211).  NaN compares false.
     const S px = st[F_POS + 0], py = st[F_POS + 1], pz = st[F_POS + 2];
@@ -664,8 +742,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
     // the gym's stored target and reset (the smooth variant is the gym env
-    // behind a motor lag)
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH;
+    // behind a motor lag; the tag variant carries the gym's target unread)
+    constexpr bool TAG = VAR == DR_VARIANT_TAG;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
@@ -708,12 +787,22 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     S cen[3];
     float mp[9], tvel[3];
     float fm[4], dev_sq = 0.f;      // smooth: motor forces, |command - force|^2
-    const float *const ext = SMOOTH ? fm : tvel;   // the obs past the gym's 15
+    // tag: the partner's position / velocity, the obs past the first 12, the
+    // role (env ids 2j pursue; i and env_id_offset + i have one parity)
+    S pp[3], pv[3];
+    float tx[7];
+    const bool pursuer = (i & 1) == 0;
+    const float sigma = pursuer ? 1.0f : -1.0f;
+    const float *const ext = TAG ? tx : (SMOOTH ? fm : tvel);   // the obs past the gym's 15
     if constexpr (SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
-    if constexpr (GYMSTATE) {
+    if constexpr (TAG) {
+        // nothing in the step reads the stored target: a reset writes it
+#pragma unroll
+        for (int k = F_TGT; k < F_N; ++k) st[k] = (S)0;
+    } else if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = ld_in<NTL>(at(fp.p[k], i));
     } else if constexpr (VAR == DR_VARIANT_MOVING) {
@@ -774,12 +863,30 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     }
     DR_STAMP(2);
     step += 1;                                             // (155)
-    const bool done = live && (crash || (step >= v.max_steps));   // (156-157)
+    bool done, any_crash = crash;   // any_crash: own or (tag) the partner's
+    if constexpr (TAG) {
+        // Wave-uniform code (dead lanes ran the physics on row n - 1, and
+        // their partners are dead too): exchange the new position and
+        // velocity and the own crash / done flags, then the pair's reward
+        // and its common end.
+        const int own = (int)crash | ((int)(crash || (step >= v.max_steps)) << 1);
+        tag_partner(st, pp, pv);
+        const int oth = partner_of(own);
+        r = tag_reward(st, pp, va.radius, pursuer);
+        any_crash = crash || (oth & 1);
+        done = live && (((own | oth) & 2) != 0);
+    } else {
+        done = live && (crash || (step >= v.max_steps));   // (156-157)
+    }
     float rf = (float)r;                                   // SB3 f32 buffer
     if constexpr (SMOOTH) {
         // uniform branch: at lam == 0 the reward is the gym's even where
         // dev_sq overflowed
         if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
+    }
+    if constexpr (TAG) {
+        // uniform branch, one f32 subtract for the lanes that crashed
+        if (va.crash != 0.f) rf = crash ? rf - va.crash : rf;
     }
 #if DR_LOADS_LANDED
     // Every value loaded up front has landed before the first store is
@@ -792,14 +899,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // in the reset branch and again where it rejoins, for every wave.
     asm volatile("" ::"v"(step), "v"(ep_old), "v"(eps_old), "v"(ret0), "v"(len0));
 #pragma unroll
-    for (int k = 0; k < F_N; ++k) asm volatile("" ::"v"(st[k]));
+    for (int k = 0; k < (TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
 #endif
     if (live) {
         st_out(at(io.rew, i), rf);
         st_out(at(io.done, i), (uint8_t)done);
     }
 #if !DR_OBS_ONCE
-    make_obs<S, OD>(st, ob, ext);
+    make_obs<S, VAR>(st, ob, ext);
 #endif
 
     float ret = 0.f;
@@ -813,7 +920,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             // DummyVecEnv: keep the terminal obs, reset in the same step.
             if (io.term_obs) {
 #if DR_OBS_ONCE
-                make_obs<S, OD>(st, ob, ext);
+                // tag: the partner's terminal state, exchanged before the branch
+                if constexpr (TAG) tag_ext(st, pp, pv, sigma, tx);
+                make_obs<S, VAR>(st, ob, ext);
 #endif
 #pragma unroll
                 for (int k = 0; k < OD; ++k) io.term_obs[i * OD + k] = ob[k];
@@ -837,17 +946,25 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                 moving_target(cen, mp, 0, (float)v.dt, &st[F_TGT], tvel);
             }
 #if !DR_OBS_ONCE
-            make_obs<S, OD>(st, ob, ext);
+            make_obs<S, VAR>(st, ob, ext);
 #endif
         }
+    }
+    if constexpr (TAG) {
+        // The reset branch has rejoined: the partner's state once more, now
+        // post-reset (both members of a pair reset in the same step).  Skipped,
+        // wave-uniformly, when no lane reset: the values are those of the
+        // first exchange.
+        if (__any(done && io.auto_reset)) tag_partner(st, pp, pv);
+        tag_ext(st, pp, pv, sigma, tx);
     }
 #if DR_OBS_ONCE
     // ONE observation pass over the post-reset state (the terminal obs is
     // formed inside the reset branch only when the caller keeps it)
-    make_obs<S, OD>(st, ob, ext);
+    make_obs<S, VAR>(st, ob, ext);
 #endif
     if constexpr (MON) {
-        if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !crash);
+        if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !any_crash);
         if (done) {               // VecMonitor: report, then restart counters
             *at(io.ep_ret_out, i) = ret;
             *at(io.ep_len_out, i) = len;
@@ -921,7 +1038,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                                                                 VarArgs<VAR> va) {
     constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH;
+    constexpr bool TAG = VAR == DR_VARIANT_TAG;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
@@ -941,7 +1059,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     // smooth: the motor forces, carried in registers over the launch, and
     // this step's |command - force|^2
     float fm[4], dev_sq = 0.f;
-    const float *const ext = SMOOTH ? fm : tvel;
+    // tag: the obs past the first 12 and the role (env_step_kernel)
+    float tx[7];
+    const bool pursuer = (i & 1) == 0;
+    const float sigma = pursuer ? 1.0f : -1.0f;
+    const float *const ext = TAG ? tx : (SMOOTH ? fm : tvel);
     if constexpr (SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
@@ -1013,12 +1135,28 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         if constexpr (VAR == DR_VARIANT_MOVING)
             moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
         bool crash;
-        const S r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
+        S r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
-        const bool done = live && (crash || (step >= max_steps));
+        bool done;
+        S pp[3], pv[3];
+        if constexpr (TAG) {
+            // wave-uniform: the exchanges of env_step_kernel, all in registers
+            // (no global store is added to the step)
+            const int own = (int)crash | ((int)(crash || (step >= max_steps)) << 1);
+            tag_partner(st, pp, pv);
+            const int oth = partner_of(own);
+            r = tag_reward(st, pp, va.radius, pursuer);
+            done = live && (((own | oth) & 2) != 0);
+        } else {
+            done = live && (crash || (step >= max_steps));
+        }
         const int64_t row = (int64_t)t * n_;
         if (live) {
-            if constexpr (SMOOTH) {
+            if constexpr (TAG) {
+                float rf = (float)r;
+                if (va.crash != 0.f) rf = crash ? rf - va.crash : rf;
+                st_out(at(io.rew + row, i), rf);
+            } else if constexpr (SMOOTH) {
                 float rf = (float)r;
                 // uniform branch, as in env_step_kernel
                 if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
@@ -1050,7 +1188,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 if (ep_num % 2000 == 0) eps += 0.1;
             }
         }
-        make_obs<S, OD>(st, ob, ext);
+        if constexpr (TAG) {
+            // rejoined: the partner's post-reset state (env_step_kernel)
+            if (__any(done && io.auto_reset)) tag_partner(st, pp, pv);
+            tag_ext(st, pp, pv, sigma, tx);
+        }
+        make_obs<S, VAR>(st, ob, ext);
         if (!live) {
 #pragma unroll
             for (int k = 0; k < OD; ++k) ob[k] = 0.f;
@@ -1428,7 +1571,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
                 if (ep_num % 2000 == 0) eps += 0.1;
             }
         }
-        make_obs<S, OD>(st, ob, tvel);
+        make_obs<S, VAR>(st, ob, tvel);
         if (!live) {
 #pragma unroll
             for (int k = 0; k < OD; ++k) ob[k] = 0.f;
@@ -1842,7 +1985,40 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
     const int64_t base = (int64_t)blockIdx.x * kBlock;
     const int64_t i = base + threadIdx.x;
     float ob[OD];
-    if (i < v.n) {
+    if constexpr (VAR == DR_VARIANT_TAG) {
+        // Each drone resets as the gym's does; a pair resets if either
+        // member's mask byte is set (n is even: i ^ 1 < n).  The partner's
+        // fresh state comes from a lane exchange outside the `in` branch,
+        // never from memory another lane writes in this launch.
+        const bool in = i < v.n;
+        S st[F_N] = {};
+        if (in) {
+            if (init) {
+                v.ep_num[i] = 0;
+                v.eps[i] = 0.0;
+                v.ep_ret[i] = 0.f;
+                v.ep_len[i] = 0;
+            }
+            if ((mask == nullptr) || mask[i] || mask[i ^ 1]) {
+                gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
+#pragma unroll
+                for (int k = 0; k < F_N; ++k) v.field(k)[i] = st[k];
+                v.step[i] = 0;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 12; ++k) st[k] = v.field(k)[i];
+            }
+        }
+        S pp[3], pv[3];
+        float tx[7];
+        tag_partner(st, pp, pv);
+        tag_ext(st, pp, pv, (i & 1) == 0 ? 1.0f : -1.0f, tx);
+        make_obs<S, VAR>(st, ob, tx);
+        if (!in) {
+#pragma unroll
+            for (int k = 0; k < OD; ++k) ob[k] = 0.f;
+        }
+    } else if (i < v.n) {
         if (init) {
             v.ep_num[i] = 0;
             v.eps[i] = 0.0;
@@ -1886,9 +2062,9 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
             float fm[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) fm[k] = v.mot[k * v.stride + i];
-            make_obs<S, OD>(st, ob, fm);
+            make_obs<S, VAR>(st, ob, fm);
         } else {
-            make_obs<S, OD>(st, ob, tvel);
+            make_obs<S, VAR>(st, ob, tvel);
         }
     } else {
 #pragma unroll
@@ -2023,6 +2199,9 @@ struct dr_handle {
     // DR_VARIANT_SMOOTH (dr_set_smoothing): passed to each launch
     float alpha = 1.0f;
     float rate_penalty = 0.0f;
+    // DR_VARIANT_TAG (dr_set_tag): passed to each launch
+    float tag_radius = 0.25f;
+    float crash_penalty = 0.0f;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -2079,10 +2258,12 @@ size_t state_bytes(int64_t stride, int dtype, int variant) {
 
 inline hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
 
-// The variant's trailing kernel argument (empty but for the smooth variant).
+// The variant's trailing kernel argument (empty but for the smooth and tag
+// variants).
 template <int VAR>
 VarArgs<VAR> var_args(const dr_handle *h) {
     if constexpr (VAR == DR_VARIANT_SMOOTH) return VarArgs<VAR>{h->alpha, h->rate_penalty};
+    else if constexpr (VAR == DR_VARIANT_TAG) return VarArgs<VAR>{h->tag_radius, h->crash_penalty};
     else return VarArgs<VAR>{};
 }
 
@@ -2110,6 +2291,9 @@ int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
     if (h->cfg.variant == DR_VARIANT_SMOOTH)
         return f64 ? launch_reset<double, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st)
                    : launch_reset<float, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st);
+    if (h->cfg.variant == DR_VARIANT_TAG)
+        return f64 ? launch_reset<double, DR_VARIANT_TAG>(h, mask, obs, mode, init, st)
+                   : launch_reset<float, DR_VARIANT_TAG>(h, mask, obs, mode, init, st);
     return f64 ? launch_reset<double, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st)
                : launch_reset<float, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st);
 }
@@ -2173,6 +2357,9 @@ int dispatch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
     if (h->cfg.variant == DR_VARIANT_SMOOTH)
         return f64 ? launch_step<double, DR_VARIANT_SMOOTH, MON>(h, io, st)
                    : launch_step<float, DR_VARIANT_SMOOTH, MON>(h, io, st);
+    if (h->cfg.variant == DR_VARIANT_TAG)
+        return f64 ? launch_step<double, DR_VARIANT_TAG, MON>(h, io, st)
+                   : launch_step<float, DR_VARIANT_TAG, MON>(h, io, st);
     return f64 ? launch_step<double, DR_VARIANT_VECTORIZED, MON>(h, io, st)
                : launch_step<float, DR_VARIANT_VECTORIZED, MON>(h, io, st);
 }
@@ -2197,17 +2384,19 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
         const char *r = std::getenv("DRONERL_ROLLOUT_WS");
         return r ? (std::atoi(r) != 0 ? 1 : 0) : -1;
     }();
-    // The smooth variant has the one-role kernel only (its lag state is not
-    // built into the warp-specialised forms), whatever the override says.
-    const bool ws = VAR == DR_VARIANT_SMOOTH
+    // The smooth and tag variants have the one-role kernel only (the lag state
+    // and the partner exchange are not built into the warp-specialised
+    // forms), whatever the override says.
+    constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG;
+    const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
                                        : h->n <= (int64_t)kWsEnvs * device_cu_count());
     // with events: hipExtLaunchKernelGGL binds them to the dispatch packet's
     // own start / end timestamps (no extra packets in the queue)
     if (ws) {
-        if constexpr (VAR == DR_VARIANT_SMOOTH) {
-            // unreachable: ws is false for this variant
+        if constexpr (ONE_ROLE) {
+            // unreachable: ws is false for these variants
         } else if constexpr (VAR == DR_VARIANT_GYM && !GEN) {
             // the split-physics form of the warp-specialised kernel (gym
             // variant, actions read from HBM; with the in-kernel policy its
@@ -2258,6 +2447,9 @@ int dispatch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent
     if (h->cfg.variant == DR_VARIANT_SMOOTH)
         return f64 ? launch_rollout<double, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1)
                    : launch_rollout<float, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1);
+    if (h->cfg.variant == DR_VARIANT_TAG)
+        return f64 ? launch_rollout<double, DR_VARIANT_TAG, GEN>(h, io, st, e0, e1)
+                   : launch_rollout<float, DR_VARIANT_TAG, GEN>(h, io, st, e0, e1);
     return f64 ? launch_rollout<double, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1)
                : launch_rollout<float, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1);
 }
@@ -2300,7 +2492,8 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     dr_config cfg = *cfg_in;
     if (cfg.num_envs < 1) return fail(nullptr, DR_ERR_INVALID, "dr_create: num_envs must be >= 1");
     if (cfg.variant != DR_VARIANT_GYM && cfg.variant != DR_VARIANT_VECTORIZED &&
-        cfg.variant != DR_VARIANT_MOVING && cfg.variant != DR_VARIANT_SMOOTH)
+        cfg.variant != DR_VARIANT_MOVING && cfg.variant != DR_VARIANT_SMOOTH &&
+        cfg.variant != DR_VARIANT_TAG)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown variant");
     if (cfg.state_dtype != DR_STATE_F64 && cfg.state_dtype != DR_STATE_F32)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown state_dtype");
@@ -2310,6 +2503,10 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     // 16 B x 2^28 = 4 GiB); shard larger batches over several handles
     if (cfg.num_envs > (int64_t)1 << 28)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: num_envs above 2^28 per handle");
+    // envs 2j and 2j+1 (global ids) are a pair, and a pair shares a wave
+    if (cfg.variant == DR_VARIANT_TAG && ((cfg.num_envs & 1) || (cfg.env_id_offset & 1)))
+        return fail(nullptr, DR_ERR_INVALID,
+                    "dr_create: DR_VARIANT_TAG needs even num_envs and env_id_offset");
     if (cfg.max_steps == 0) cfg.max_steps = cfg.variant == DR_VARIANT_VECTORIZED ? 1000 : 200;
     if (cfg.max_steps < 0) return fail(nullptr, DR_ERR_INVALID, "dr_create: max_steps < 0");
     if (cfg.dt == 0.0) cfg.dt = kDt;
@@ -2333,7 +2530,10 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
                      ? 15
                      : (cfg.variant == DR_VARIANT_MOVING
                             ? 18
-                            : (cfg.variant == DR_VARIANT_SMOOTH ? 19 : 12));
+                            : ((cfg.variant == DR_VARIANT_SMOOTH ||
+                                cfg.variant == DR_VARIANT_TAG)
+                                   ? 19
+                                   : 12));
     // Launch form by batch size, from the measured sweep
     // (scripts/micro/ab_sweep.sh, profiles/r01_env_launch_sweep.txt):
     // [0, 384k) 64 rows/wave; [384k, 1.5M) 32 + nontemporal state loads;
@@ -2628,6 +2828,28 @@ int dr_get_smoothing(const dr_handle *h, float *alpha, float *rate_penalty) {
     if (h->cfg.variant != DR_VARIANT_SMOOTH) return DR_ERR_UNSUPPORTED;
     if (alpha) *alpha = h->alpha;
     if (rate_penalty) *rate_penalty = h->rate_penalty;
+    return DR_OK;
+}
+
+int dr_set_tag(dr_handle *h, float tag_radius, float crash_penalty) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_tag: null handle");
+    // written so that NaN fails every test
+    if (!(tag_radius > 0.0f && tag_radius <= 3.4028234663852886e38f))
+        return fail(h, DR_ERR_INVALID, "dr_set_tag: tag_radius must be finite and > 0");
+    if (!(crash_penalty >= 0.0f && crash_penalty <= 3.4028234663852886e38f))
+        return fail(h, DR_ERR_INVALID, "dr_set_tag: crash_penalty must be finite and >= 0");
+    if (h->cfg.variant != DR_VARIANT_TAG)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_tag: only DR_VARIANT_TAG has pairs");
+    h->tag_radius = tag_radius;
+    h->crash_penalty = crash_penalty;
+    return DR_OK;
+}
+
+int dr_get_tag(const dr_handle *h, float *tag_radius, float *crash_penalty) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_tag: null handle");
+    if (h->cfg.variant != DR_VARIANT_TAG) return DR_ERR_UNSUPPORTED;
+    if (tag_radius) *tag_radius = h->tag_radius;
+    if (crash_penalty) *crash_penalty = h->crash_penalty;
     return DR_OK;
 }
 

@@ -25,14 +25,18 @@ ARM_LENGTH = 0.5
 K_YAW = 0.01
 MAX_STEPS = 200
 MOTOR_MAX = 3 * MASS * G / 4.0          # 7.3575, action_space.high
-OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18, "smooth": 19}
+OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18, "smooth": 19, "tag": 19}
 # the force each motor applies after a reset of the "smooth" variant
 # (DESIGN.md section 14): f32(mass * g / 4)
 HOVER = float(np.float32(MASS * G / 4.0))
 # reset uniforms per env and reset for rng="host" 
-RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14, "smooth": 5}
+RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14, "smooth": 5, "tag": 5}
 _VARIANT_ID = {"gym": _lib.DR_VARIANT_GYM, "vectorized": _lib.DR_VARIANT_VECTORIZED,
-               "moving": _lib.DR_VARIANT_MOVING, "smooth": _lib.DR_VARIANT_SMOOTH}
+               "moving": _lib.DR_VARIANT_MOVING, "smooth": _lib.DR_VARIANT_SMOOTH,
+               "tag": _lib.DR_VARIANT_TAG}
+# the "tag" variant's defaults
+TAG_RADIUS = 0.25
+CRASH_PENALTY = 0.0
 
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
 # (N, width) f32 fields a single variant owns
@@ -52,6 +56,29 @@ def check_smoothing(variant: str, motor_alpha: float, rate_penalty: float) -> No
         raise ValueError(f"motor_alpha / rate_penalty need variant='smooth', not {variant!r}")
 
 
+def check_tag(variant: str, tag_radius, crash_penalty, num_envs: int | None = None,
+              env_id_offset: int = 0) -> tuple[float, float]:
+    """The argument rules of the "tag" variant (dr_create / dr_set_tag), raised
+    as ValueError before any device work: tag_radius finite and > 0,
+    crash_penalty finite and >= 0, both None (the variant's defaults) on every
+    other variant, and an even number of drones at an even env_id_offset.
+    Returns the two values with the defaults filled in."""
+    if variant != "tag":
+        if tag_radius is not None or crash_penalty is not None:
+            raise ValueError(f"tag_radius / crash_penalty need variant='tag', not {variant!r}")
+        return TAG_RADIUS, CRASH_PENALTY
+    r = TAG_RADIUS if tag_radius is None else float(tag_radius)
+    c = CRASH_PENALTY if crash_penalty is None else float(crash_penalty)
+    if not (0.0 < r < float("inf")):
+        raise ValueError(f"tag_radius must be finite and > 0, got {tag_radius!r}")
+    if not (0.0 <= c < float("inf")):
+        raise ValueError(f"crash_penalty must be finite and >= 0, got {crash_penalty!r}")
+    if num_envs is not None and (int(num_envs) % 2 or int(env_id_offset) % 2):
+        raise ValueError("variant='tag' pairs env 2j with env 2j+1: num_envs and env_id_offset "
+                         f"must be even, got {num_envs!r} and {env_id_offset!r}")
+    return r, c
+
+
 def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -64,6 +91,9 @@ class DroneBatch:
                moving-target curriculum of BASELINE configs[4]; 18-d obs)
                or "smooth" (the gym env behind a first-order motor lag with
                an action-rate penalty; 19-d obs)
+               or "tag" (envs 2j / 2j+1 are a pursuer / evader pair with a
+               zero-sum reward; 19-d obs; num_envs
+               counts drones and is even)
     dtype      torch.float64 (reference precision) or torch.float32 state
     rng        "philox" (counter-based, seeded) or "host" (caller supplies
                the reset uniforms: numpy-MT19937 replay for parity tests)
@@ -73,6 +103,10 @@ class DroneBatch:
                "smooth" only: the lag blend alpha = dt / (tau + dt) in (0, 1]
                and the penalty on |command - motor force|^2 (>= 0).  At the
                defaults (1, 0) the variant is "gym" bit for bit.
+    tag_radius, crash_penalty
+               "tag" only: the distance inside which the pursuer collects its
+               bonus (> 0) and what a crashing drone pays (>= 0).  None = the
+               variant's defaults (0.25, 0).
     """
 
     def __init__(self, num_envs: int, variant: str = "gym",
@@ -80,10 +114,13 @@ class DroneBatch:
                  auto_reset: bool = True, rng: str = "philox",
                  env_id_offset: int = 0, max_steps: int | None = None,
                  keep_terminal_obs: bool = False, monitor: bool = False,
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
+                 tag_radius: float | None = None, crash_penalty: float | None = None):
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
         check_smoothing(variant, motor_alpha, rate_penalty)
+        tag_radius, crash_penalty = check_tag(variant, tag_radius, crash_penalty, num_envs,
+                                              env_id_offset)
         if dtype not in (torch.float64, torch.float32):
             raise ValueError("dtype must be torch.float64 or torch.float32")
         if rng not in ("philox", "host"):
@@ -127,6 +164,9 @@ class DroneBatch:
         self.motor_alpha, self.rate_penalty = 1.0, 0.0
         if variant == "smooth":
             self.set_smoothing(motor_alpha, rate_penalty)
+        self.tag_radius, self.crash_penalty = TAG_RADIUS, CRASH_PENALTY
+        if variant == "tag":
+            self.set_tag(tag_radius, crash_penalty)
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -368,6 +408,20 @@ class DroneBatch:
         check(self.L.dr_set_smoothing(self.handle, float(motor_alpha), float(rate_penalty)),
               self.handle)
         self.motor_alpha, self.rate_penalty = float(motor_alpha), float(rate_penalty)
+
+    def set_tag(self, tag_radius: float | None = None,
+                crash_penalty: float | None = None) -> None:
+        """variant="tag": new tag radius and crash penalty (None = the default)
+        for every step / rollout enqueued after the call (a captured graph
+        keeps the values it was captured with)."""
+        if self.variant != "tag":
+            raise ValueError(f"set_tag needs variant='tag', not {self.variant!r}")
+        r, c = check_tag(self.variant, tag_radius, crash_penalty)
+        check(self.L.dr_set_tag(self.handle, r, c), self.handle)
+        # what the kernels see: the f32 values
+        rr, cc = ctypes.c_float(), ctypes.c_float()
+        check(self.L.dr_get_tag(self.handle, ctypes.byref(rr), ctypes.byref(cc)), self.handle)
+        self.tag_radius, self.crash_penalty = float(rr.value), float(cc.value)
 
     def set_reset_uniforms(self, u) -> None:
         """rng='host': (N,5) f64 uniforms ((N,14) for "moving") consumed by

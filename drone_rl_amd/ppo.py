@@ -94,10 +94,17 @@ class PPOConfig:
     # The neutral values (1, 0) are the gym env; anything else needs the variant
     motor_alpha: float = 1.0
     rate_penalty: float = 0.0
+    # variant "tag" (num_envs counts drones, even): the
+    # radius inside which the pursuer collects its bonus and what a crashing
+    # drone pays.  None = the variant's defaults (0.25, 0); a value needs the
+    # variant.  One shared policy flies both roles (the role is obs[18])
+    tag_radius: float | None = None
+    crash_penalty: float | None = None
 
     def __post_init__(self):
-        from .env import check_smoothing
+        from .env import check_smoothing, check_tag
         check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
+        check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -128,7 +135,8 @@ class PPOTrainer:
                               env_id_offset=D.env_shard(rank, N)[0], monitor=True,
                               keep_terminal_obs=cfg.bootstrap_timeouts,
                               dtype=torch.float64 if cfg.state_dtype == "f64" else torch.float32,
-                              motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty)
+                              motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty,
+                              tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty)
         if cfg.initial_eps:
             self.env.set("eps", torch.full((N,), float(cfg.initial_eps), dtype=torch.float64))
         od = self.env.obs_dim
@@ -317,6 +325,7 @@ class PPOTrainer:
         c = self.cfg
         if kind == "rollout":
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
+                    self.env.tag_radius, self.env.crash_penalty,
                     self.env.motor_alpha, self.env.rate_penalty)
         o = self.opt
         return (c.seed, self.rank, c.n_epochs, c.batch_size, c.clip_range, c.ent_coef,
@@ -538,15 +547,28 @@ class PPOTrainer:
 
     def episode_stats(self):
         """Mean return / length of the episodes that ended in the last rollout
-        (VecMonitor's ep_info_buffer role; all-reduced over ranks)."""
+        (VecMonitor's ep_info_buffer role; all-reduced over ranks).  Variant
+        "tag" adds the mean return per role: the reward is zero-sum, so the
+        mean over both roles says nothing."""
         done = self.dones[1:].bool()
-        s = torch.stack([torch.where(done, self.ep_ret, 0).sum(),
-                         torch.where(done, self.ep_len, 0).sum().float(),
-                         done.sum().float()])
+        terms = [torch.where(done, self.ep_ret, 0).sum(),
+                 torch.where(done, self.ep_len, 0).sum().float(),
+                 done.sum().float()]
+        tag = self.cfg.variant == "tag"
+        if tag:
+            # even envs pursue, odd envs evade (a rank's shard starts even)
+            for role in (0, 1):
+                d = done[:, role::2]
+                terms += [torch.where(d, self.ep_ret[:, role::2], 0).sum(), d.sum().float()]
+        s = torch.stack(terms)
         D.allreduce_sum_(s, self.world, group=self.pg)
         n = max(s[2].item(), 1.0)
-        return {"ep_rew_mean": s[0].item() / n, "ep_len_mean": s[1].item() / n,
-                "episodes": int(s[2].item())}
+        out = {"ep_rew_mean": s[0].item() / n, "ep_len_mean": s[1].item() / n,
+               "episodes": int(s[2].item())}
+        if tag:
+            out["ep_rew_mean_pursuer"] = s[3].item() / max(s[4].item(), 1.0)
+            out["ep_rew_mean_evader"] = s[5].item() / max(s[6].item(), 1.0)
+        return out
 
     def learn(self, total_timesteps: int, log_every: int = 1, logger=print):
         t0 = time.perf_counter()

@@ -61,9 +61,14 @@ def main(argv=None):
     ap.add_argument("--net", type=int, nargs="+", default=[256, 256])
     ap.add_argument("--state-dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--variant", choices=["gym", "moving", "smooth"], default="gym",
+    ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag"], default="gym",
                     help="gym = DroneGymEnv; moving = the moving-target curriculum; "
-                         "smooth = gym behind a motor lag with an action-rate penalty")
+                         "smooth = gym behind a motor lag with an action-rate penalty; "
+                         "tag = pursuer / evader pairs, self-play with one shared policy")
+    ap.add_argument("--tag-radius", type=float, default=None,
+                    help="--variant tag: the pursuer's bonus radius in m (default 0.25)")
+    ap.add_argument("--crash-penalty", type=float, default=None,
+                    help="--variant tag: what a crashing drone pays (default 0)")
     ap.add_argument("--motor-alpha", type=float, default=1.0,
                     help="--variant smooth: lag blend dt / (tau + dt) in (0, 1] (1 = no lag)")
     ap.add_argument("--rate-penalty", type=float, default=0.0,
@@ -103,6 +108,7 @@ def main(argv=None):
                   state_dtype=a.state_dtype, variant=a.variant, initial_eps=a.initial_eps,
                   bootstrap_timeouts=a.bootstrap_timeouts,
                   motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty,
+                  tag_radius=a.tag_radius, crash_penalty=a.crash_penalty,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

@@ -48,14 +48,16 @@ class BatchedDroneVecEnv(_VecEnvBase):
     def __init__(self, num_envs: int = 1, variant: str = "gym",
                  dtype: torch.dtype = torch.float64, device=None, seed: int | None = None,
                  monitor: bool = True, rng: str = "philox", env_id_offset: int = 0,
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
+                 tag_radius: float | None = None, crash_penalty: float | None = None):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=(variant != "vectorized"), rng=rng,
                                 env_id_offset=env_id_offset, keep_terminal_obs=True,
                                 monitor=True, motor_alpha=motor_alpha,
-                                rate_penalty=rate_penalty)
+                                rate_penalty=rate_penalty, tag_radius=tag_radius,
+                                crash_penalty=crash_penalty)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)

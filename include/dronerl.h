@@ -67,7 +67,19 @@ enum dr_variant {
        runs the gym step on f' and reports reward - rate_penalty * s;
        obs (N,19) = gym obs + f'.  alpha / rate_penalty: dr_set_smoothing;
        at their defaults (1, 0) the variant is DR_VARIANT_GYM bit for bit. */
-    DR_VARIANT_SMOOTH = 3
+    DR_VARIANT_SMOOTH = 3,
+    /* Tag (an extension with no reference oracle, spec in DESIGN.md section
+       15): envs 2j (pursuer, role +1) and 2j+1 (evader, role -1) of the
+       global numbering form a pair; num_envs and env_id_offset must be even.
+       Each drone flies the gym dynamics on its own action.  With d the
+       distance between the partners' new positions, the pursuer's reward is
+       g = 0.01 * (-d), plus 1 while d < tag_radius, the evader's is -g, and a
+       drone that crashes pays crash_penalty on top.  A pair's episode ends
+       for both when either crashes or reaches the step limit; both reset as
+       the gym env does.  obs (N,19) = the gym's first 12, partner - own
+       position, partner - own velocity, the role.  tag_radius /
+       crash_penalty: dr_set_tag (defaults 0.25, 0). */
+    DR_VARIANT_TAG = 4
 };
 
 enum dr_state_dtype {
@@ -138,7 +150,7 @@ int dr_create(const dr_config *cfg, dr_handle **out);
 int dr_destroy(dr_handle *h);
 
 int64_t dr_num_envs(const dr_handle *h);
-int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving, 19 smooth */
+int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving, 19 smooth / tag */
 
 /* Reset every env and write (N,obs_dim) obs.  Replaces DroneEnv.reset
    (drone.py:48-75) called on each env by VecEnv.reset, and
@@ -147,7 +159,8 @@ int dr_reset(dr_handle *h, float *obs_out, void *stream);
 
 /* Reset only envs with mask[i] != 0 ((N,) u8); obs_out rows of other envs are
    rewritten with their current obs.  (DummyVecEnv-free callers, test
-   harnesses.)  Not available for the vectorized variant. */
+   harnesses.)  Not available for the vectorized variant.  DR_VARIANT_TAG
+   resets a pair (envs 2j, 2j+1) if either member's byte is set. */
 int dr_reset_masked(dr_handle *h, const uint8_t *mask, float *obs_out,
                     void *stream);
 
@@ -214,6 +227,14 @@ int dr_set_seed(dr_handle *h, uint64_t seed);
    dr_get_smoothing reads them back (either pointer may be NULL). */
 int dr_set_smoothing(dr_handle *h, float alpha, float rate_penalty);
 int dr_get_smoothing(const dr_handle *h, float *alpha, float *rate_penalty);
+
+/* DR_VARIANT_TAG: the tag radius (> 0, default 0.25) and the crash penalty
+   (>= 0, default 0).  DR_ERR_INVALID for a null handle, values out of range or
+   non-finite; DR_ERR_UNSUPPORTED on the other variants.  Takes effect for work
+   enqueued after the call (launch arguments, not device state).  dr_get_tag
+   reads them back (either pointer may be NULL). */
+int dr_set_tag(dr_handle *h, float tag_radius, float crash_penalty);
+int dr_get_tag(const dr_handle *h, float *tag_radius, float *crash_penalty);
 
 /* Synthetic random policy: out (n,4) f32 i.i.d. U[lo,hi) from Philox keyed
    by seed with counter (env_id_offset + i, step).  Not part of the

@@ -15,6 +15,12 @@ command at once, so the force before a step is the previous clipped command,
 or HOVER on the first step of an episode -- what the smooth variant holds at
 its neutral parameters.
 
+A checkpoint trained on variant "tag"  is evaluated
+in self-play on that variant with the tag_radius / crash_penalty of its
+config: per role the mean return of the episodes that ended and the share of
+them in which that drone crashed, and per pair tag_fraction (the share of
+steps with the two closer than tag_radius) and the mean distance.
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
 """
 import argparse
@@ -28,7 +34,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM  # noqa: E402
+from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM, check_tag  # noqa: E402
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
@@ -84,6 +90,56 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
             "cmd_dev_sq_mean": dev_sq / steps}
 
 
+@torch.no_grad()
+def evaluate_tag(ckpt, envs, steps, seed, deterministic):
+    sd = torch.load(ckpt, map_location="cpu", weights_only=True)
+    cfg = sd["config"]
+    dev = torch.device("cuda", 0)
+    pol = ActorCritic(OBS_DIM["tag"], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
+    pol.flat.data.copy_(sd["flat"].to(dev))
+    env = DroneBatch(envs, "tag", device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
+                     keep_terminal_obs=True, tag_radius=cfg.get("tag_radius"),
+                     crash_penalty=cfg.get("crash_penalty"))
+    obs = env.reset().clone()
+    infer = PolicyInference(pol, envs)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    std = pol.log_std.exp()
+    ep_ret = torch.empty(envs, device=dev)
+    ep_len = torch.empty(envs, dtype=torch.int32, device=dev)
+    # per role (0 pursuer, 1 evader): return sum, episodes, own crashes
+    ret = [0.0, 0.0]
+    eps_n = [0.0, 0.0]
+    crashed = [0.0, 0.0]
+    len_sum = tagged = dist = 0.0
+    for _ in range(steps):
+        mean, _ = infer(obs)
+        a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
+                                                                 device=dev)
+        env.ep_ret, env.ep_len = ep_ret, ep_len
+        o, r, d = env.step(a.clamp(0.0, MOTOR_MAX).contiguous())
+        obs = o.clone()
+        db = d.bool()
+        # the state the step ended in: the terminal obs where the pair was reset
+        end = torch.where(db[:, None], env.term_obs, o)
+        own_crash = db & ((end[:, 2] < 0) | (end[:, :3].square().sum(1) > 2500.0))
+        dd = end[0::2, 12:15].norm(dim=1)
+        tagged += float((dd < env.tag_radius).float().mean())
+        dist += float(dd.mean())
+        len_sum += float(ep_len[db].float().sum())
+        for role in (0, 1):
+            m = db[role::2]
+            ret[role] += float(ep_ret[role::2][m].sum())
+            eps_n[role] += float(m.sum())
+            crashed[role] += float(own_crash[role::2].sum())
+    env.close()
+    n = [max(x, 1.0) for x in eps_n]
+    return {"deterministic": deterministic, "episodes": int(eps_n[0]),
+            "ep_len_mean": len_sum / max(eps_n[0] + eps_n[1], 1.0),
+            "ep_rew_mean_pursuer": ret[0] / n[0], "ep_rew_mean_evader": ret[1] / n[1],
+            "crash_frac_pursuer": crashed[0] / n[0], "crash_frac_evader": crashed[1] / n[1],
+            "tag_fraction": tagged / steps, "pair_distance_mean": dist / steps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("ckpt")
@@ -98,9 +154,13 @@ def main():
     if out["variant"] == "smooth":
         out["motor_alpha"] = cfg.get("motor_alpha", 1.0)
         out["rate_penalty"] = cfg.get("rate_penalty", 0.0)
+    if out["variant"] == "tag":
+        out["tag_radius"], out["crash_penalty"] = check_tag("tag", cfg.get("tag_radius"),
+                                                            cfg.get("crash_penalty"))
     for det in (True, False):
-        out["deterministic" if det else "sampled"] = evaluate(a.ckpt, a.eps, a.envs, a.steps,
-                                                               a.seed, det)
+        out["deterministic" if det else "sampled"] = (
+            evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det) if out["variant"] == "tag"
+            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det))
     print(json.dumps(out), flush=True)
 
 

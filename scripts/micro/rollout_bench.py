@@ -3,6 +3,7 @@ replayed dr_step launches: env-steps/s and algorithmic GB/s per launch.
 
   python scripts/micro/rollout_bench.py [--envs 65536] [--reps 20]
                                         [--variant smooth --motor-alpha 0.5 --rate-penalty 0.01]
+                                        [--variant tag --tag-radius 0.25 --crash-penalty 0.5]
 The kernel form follows dr_rollout's launch rule (DRONERL_ROLLOUT_WS=0/1 forces it)."""
 import argparse
 import json
@@ -22,14 +23,18 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--dtype", default="f64")
 ap.add_argument("--act-sets", type=int, default=1,
                 help="distinct (k,N,4) action buffers cycled over the launches")
-ap.add_argument("--variant", choices=["gym", "moving", "smooth"], default="gym")
+ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag"], default="gym")
+ap.add_argument("--tag-radius", type=float, default=None)
+ap.add_argument("--crash-penalty", type=float, default=None)
 ap.add_argument("--motor-alpha", type=float, default=1.0)
 ap.add_argument("--rate-penalty", type=float, default=0.0)
 a = ap.parse_args()
 od = OBS_DIM[a.variant]
 # variant state beyond the gym's, read and written once per launch
-extra = {"gym": 0, "moving": 9 * 4, "smooth": 2 * 4 * 4}[a.variant]
+extra = {"gym": 0, "moving": 9 * 4, "smooth": 2 * 4 * 4, "tag": 0}[a.variant]
 kw = dict(motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty) if a.variant == "smooth" else {}
+if a.variant == "tag":
+    kw = dict(tag_radius=a.tag_radius, crash_penalty=a.crash_penalty)
 dev = torch.device("cuda", 0)
 dt = torch.float64 if a.dtype == "f64" else torch.float32
 sb = 8 if a.dtype == "f64" else 4
