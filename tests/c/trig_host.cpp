@@ -18,3 +18,12 @@ extern "C" void trig_sincosf(int64_t n, const float *x, float *s, float *c) {
         c[i] = t.c;
     }
 }
+
+// The range predicates that choose between the fast path and the library.
+extern "C" void trig_fast_range(int64_t n, const double *x, uint8_t *out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = dr::sincos_fast_range(x[i]);
+}
+
+extern "C" void trig_fast_rangef(int64_t n, const float *x, uint8_t *out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = dr::sincosf_fast_range(x[i]);
+}
