@@ -28,6 +28,7 @@
 #include <hip/hip_ext.h>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "common.h"
 #include "trig.h"
@@ -46,9 +47,6 @@ constexpr double kFactor = kArm / 1.4142135623730951;  // L / np.sqrt(2)
 constexpr float kKyaw32 = 0.01f;  // python float * np.float32 -> f32 (NEP 50)
 constexpr double kDt = 0.02;
 
-#ifndef DR_STRIDE_PAD
-#define DR_STRIDE_PAD 0
-#endif
 // DR_STAMPS (diagnostic builds only): per-wave s_memrealtime / s_memtime
 // stamps at phase boundaries of env_step_kernel into a module-scope array,
 // read back by dr_diag_stamps (scripts/micro/stamps.py).  Never set in the
@@ -73,42 +71,13 @@ __device__ unsigned long long g_stamps[16384 * 8];
     do {            \
     } while (0)
 #endif
-// 1: obs staged per wave (no block barrier); 0: per block
-#ifndef DR_WAVE_STAGE
-#define DR_WAVE_STAGE 1
-#endif
-// 1 (A/B builds only; measured no gain): the Philox block of the reset draws
-// is computed for every lane right after the loads are issued (keyed by
-// ep_num + 1, loaded first), instead of in the divergent reset branch
-#ifndef DR_HOIST_RESET
-#define DR_HOIST_RESET 0
-#endif
-// waves per workgroup of env_step_kernel (A/B builds: 1, 2, 4)
-#ifndef DR_ENV_WPB
-#define DR_ENV_WPB 4
-#endif
-constexpr int kEnvBlock = 64 * DR_ENV_WPB;
+// waves per workgroup of env_step_kernel (1, 2 and 8 were measured against
+// it: docs/HISTORY.md)
+constexpr int kEnvWpb = 4;
+constexpr int kEnvBlock = 64 * kEnvWpb;
 // steps per group of the rollout kernels' next-reset Philox draw-ahead
 constexpr int kResetAhead = 8;
 
-// 1: the observation is formed once, after the auto-reset (the terminal
-// obs only when requested); 0: formed before the reset and again for the
-// reset rows
-#ifndef DR_OBS_ONCE
-#define DR_OBS_ONCE 1
-#endif
-
-// 1: per-step outputs and state are written with nontemporal stores.  They
-// stream to HBM while the kernel runs instead of sitting dirty in L2 until
-// the end-of-kernel writeback (4-9 % faster from 65,536 to 4M envs).
-// 1: the step kernel's loads are all waited for before its first store
-// (see env_step_kernel); 0 (A/B only): the compiler's own wait placement
-#ifndef DR_LOADS_LANDED
-#define DR_LOADS_LANDED 1
-#endif
-#ifndef DR_NT_STORES
-#define DR_NT_STORES 1
-#endif
 // State loads: nontemporal (NTL) only in the large-batch launch form, where
 // they measured faster; at 131,072 envs they measured 28 % slower.
 template <bool NTL, typename T>
@@ -116,10 +85,12 @@ __device__ inline T ld_in(const T *p) {
     if constexpr (NTL) return __builtin_nontemporal_load(p);
     else return *p;
 }
+// Per-step outputs and state are written with nontemporal stores.  They
+// stream to HBM while the kernel runs instead of sitting dirty in L2 until
+// the end-of-kernel writeback (4-9 % faster from 65,536 to 4M envs).
 template <typename T>
 __device__ inline void st_out(T *p, T x) {
-    if (DR_NT_STORES) store_nt(p, x);
-    else *p = x;
+    store_nt(p, x);
 }
 // N of the Euler angles at once: the fast path runs unconditionally for
 // all N (independent chains interleave; the polynomial constants are
@@ -477,18 +448,11 @@ __device__ inline float4 smooth_filter(float4 a, float f[4], float alpha, float 
 // memory.  It must execute with all 64 lanes of the wave active (a lane
 // reads what its partner holds, and an inactive partner supplies nothing),
 // so it is only ever called from wave-uniform code.
-// DR_TAG_XCHG 0: DPP quad_perm:[1,0,3,2], one v_mov_b32_dpp per dword;
-// 1 (A/B builds): __shfl_xor(., 1), a ds_bpermute_b32 per dword.
-#ifndef DR_TAG_XCHG
-#define DR_TAG_XCHG 0
-#endif
+// DPP quad_perm:[1,0,3,2], one v_mov_b32_dpp per dword (__shfl_xor(., 1), a
+// ds_bpermute_b32 per dword, measured slower: DESIGN.md section 15).
 __device__ inline int partner_of(int x) {
-#if DR_TAG_XCHG
-    return __shfl_xor(x, 1);
-#else
     // quad_perm [1,0,3,2] = 1 | 0 << 2 | 3 << 4 | 2 << 6
     return __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false);
-#endif
 }
 __device__ inline float partner_of(float x) {
     return __int_as_float(partner_of(__float_as_int(x)));
@@ -674,7 +638,7 @@ __device__ inline void store_obs_wave(float *sh_block, const float ob[OD],
     // DS ops of one wave execute in order; the barrier only pins the
     // compiler's schedule (no workgroup s_barrier is emitted)
     __builtin_amdgcn_wave_barrier();
-    const int64_t wbase = (int64_t)blockIdx.x * (DR_ENV_WPB * RPW) + w * RPW;
+    const int64_t wbase = (int64_t)blockIdx.x * (kEnvWpb * RPW) + w * RPW;
     const int64_t nvalid = (n - wbase) < RPW ? (n - wbase) : RPW;
     if (nvalid <= 0) return;
     float *dst = dst_all + wbase * OD;
@@ -761,7 +725,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     int32_t *const p_step = fp.step;
     int32_t *const p_epn = fp.ep_num;
     double *const p_eps = fp.eps;
-    const int64_t base = (int64_t)blockIdx.x * (DR_ENV_WPB * RPW);
+    const int64_t base = (int64_t)blockIdx.x * (kEnvWpb * RPW);
     const int lane_ = threadIdx.x & 63;
     // env of this lane; lanes >= RPW of a half-populated wave own none
     const int64_t i_own = lane_ < RPW ? base + (threadIdx.x >> 6) * RPW + lane_ : n_;
@@ -771,7 +735,6 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     float ob[OD];
     S st[F_N];
     int32_t ep_old = 0;
-    if constexpr (GYMLIKE && DR_HOIST_RESET) ep_old = *at(p_epn, i);
     // Issue order = landing order: euler and omega first so the three
     // sincos range reductions start while pos / vel / target are still in
     // flight (s_waitcnt vmcnt counts oldest-first).
@@ -821,7 +784,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // the measured traffic, not in the 305 B algorithmic)
     double eps_old = 0.0;
     if constexpr (GYMLIKE) {
-        if (!DR_HOIST_RESET) ep_old = *at(p_epn, i);
+        ep_old = *at(p_epn, i);
         // eps loaded with the state: the Philox reset path holds no global
         // load (6-8 % faster at 65,536-131,072 envs than loading it in the reset)
         eps_old = *at(p_eps, i);
@@ -839,15 +802,6 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // s_waitcnt holds back the issue of the remaining ones by a full memory
     // latency.
     __builtin_amdgcn_sched_barrier(0);
-    u32x4 pre0{};
-    if constexpr (GYMSTATE && DR_HOIST_RESET) {
-        if constexpr (!HU) {
-            const uint64_t gid = (uint64_t)(v.env_id_offset + i);
-            pre0 = philox4x32_10(u32x4{(uint32_t)(ep_old + 1), (uint32_t)gid,
-                                       (uint32_t)(gid >> 32), TAG_RESET},
-                                 v.seed_lo, v.seed_hi);
-        }
-    }
     if constexpr (VAR == DR_VARIANT_MOVING) {
         // the reward and obs of this step see the target at the NEW step
         moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
@@ -888,7 +842,6 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         // uniform branch, one f32 subtract for the lanes that crashed
         if (va.crash != 0.f) rf = crash ? rf - va.crash : rf;
     }
-#if DR_LOADS_LANDED
     // Every value loaded up front has landed before the first store is
     // issued (they were issued first and the physics took longer than
     // their latency, so this waits for nothing).  Without it the compiler
@@ -900,14 +853,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     asm volatile("" ::"v"(step), "v"(ep_old), "v"(eps_old), "v"(ret0), "v"(len0));
 #pragma unroll
     for (int k = 0; k < (TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
-#endif
     if (live) {
         st_out(at(io.rew, i), rf);
         st_out(at(io.done, i), (uint8_t)done);
     }
-#if !DR_OBS_ONCE
-    make_obs<S, VAR>(st, ob, ext);
-#endif
 
     float ret = 0.f;
     int32_t len = 0;
@@ -919,18 +868,15 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         if (done && io.auto_reset) {
             // DummyVecEnv: keep the terminal obs, reset in the same step.
             if (io.term_obs) {
-#if DR_OBS_ONCE
                 // tag: the partner's terminal state, exchanged before the branch
                 if constexpr (TAG) tag_ext(st, pp, pv, sigma, tx);
                 make_obs<S, VAR>(st, ob, ext);
-#endif
 #pragma unroll
                 for (int k = 0; k < OD; ++k) io.term_obs[i * OD + k] = ob[k];
             }
             step = 0;
             if constexpr (GYMSTATE) {
-                gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old,
-                               DR_HOIST_RESET ? &pre0 : nullptr);
+                gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old);
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
                 if constexpr (SMOOTH) {
@@ -945,9 +891,6 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                 for (int k = 0; k < 9; ++k) *at(v.mot + k * v.stride, i) = mp[k];
                 moving_target(cen, mp, 0, (float)v.dt, &st[F_TGT], tvel);
             }
-#if !DR_OBS_ONCE
-            make_obs<S, VAR>(st, ob, ext);
-#endif
         }
     }
     if constexpr (TAG) {
@@ -958,11 +901,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         if (__any(done && io.auto_reset)) tag_partner(st, pp, pv);
         tag_ext(st, pp, pv, sigma, tx);
     }
-#if DR_OBS_ONCE
     // ONE observation pass over the post-reset state (the terminal obs is
     // formed inside the reset branch only when the caller keeps it)
     make_obs<S, VAR>(st, ob, ext);
-#endif
     if constexpr (MON) {
         if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !any_crash);
         if (done) {               // VecMonitor: report, then restart counters
@@ -991,11 +932,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
         for (int k = 0; k < OD; ++k) ob[k] = 0.f;
     }
-#if DR_WAVE_STAGE
     store_obs_wave<OD, RPW>(reinterpret_cast<float *>(sh4), ob, io.obs, v.n);
-#else
-    store_obs_block<OD>(reinterpret_cast<float *>(sh4), ob, io.obs, base, v.n);
-#endif
     DR_STAMP(5);
 }
 
@@ -1032,6 +969,20 @@ struct RolloutIO {
     int auto_reset;
 };
 
+// The random policy's action of env `gid` at policy step `s`: one Philox word
+// per env and step under the key (k0, k1), scaled to [lo, lo + span).  The
+// rollout kernels re-declare the key opaque at every draw themselves (see
+// env_rollout_kernel): with that pin inside this function their device code
+// changed.
+__device__ inline float4 action_of(uint64_t s, uint64_t gid, uint32_t k0, uint32_t k1,
+                                   float lo, float span) {
+    const u32x4 r = philox4x32_10(
+        u32x4{(uint32_t)s, (uint32_t)(s >> 32), (uint32_t)gid, TAG_ACTION ^ (uint32_t)(gid >> 32)},
+        k0, k1);
+    return make_float4(lo + span * u01_f32(r.x), lo + span * u01_f32(r.y),
+                       lo + span * u01_f32(r.z), lo + span * u01_f32(r.w));
+}
+
 template <typename S, int VAR, int RPW, bool GEN>
 __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, RolloutIO io,
                                                                 FieldPtrs<S> fp,
@@ -1043,7 +994,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
-    const int64_t base = (int64_t)blockIdx.x * (DR_ENV_WPB * RPW);
+    const int64_t base = (int64_t)blockIdx.x * (kEnvWpb * RPW);
     const int lane_ = threadIdx.x & 63;
     const int64_t i_own = lane_ < RPW ? base + (threadIdx.x >> 6) * RPW + lane_ : n_;
     const bool live = i_own < n_;
@@ -1208,14 +1159,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             const uint64_t s = io.a_step0 + (uint64_t)t;
             uint32_t ak0 = io.a_k0, ak1 = io.a_k1;
             asm volatile("" : "+s"(ak0), "+s"(ak1));
-            const u32x4 r = philox4x32_10(
-                u32x4{(uint32_t)s, (uint32_t)(s >> 32), (uint32_t)gid,
-                      TAG_ACTION ^ (uint32_t)(gid >> 32)},
-                ak0, ak1);
-            const float4 act = make_float4(io.a_lo + io.a_span * u01_f32(r.x),
-                                           io.a_lo + io.a_span * u01_f32(r.y),
-                                           io.a_lo + io.a_span * u01_f32(r.z),
-                                           io.a_lo + io.a_span * u01_f32(r.w));
+            const float4 act = action_of(s, gid, ak0, ak1, io.a_lo, io.a_span);
             if (io.act_out && live)
                 st_out(at(reinterpret_cast<float4 *>(io.act_out) + (int64_t)t * n_, i), act);
             step_one(mix_of(act), t);
@@ -1372,7 +1316,7 @@ struct WsLds {
 template <typename S, int VAR, bool GEN>
 __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v, RolloutIO io,
                                                                     FieldPtrs<S> fp) {
-    constexpr int OD = VAR == DR_VARIANT_GYM ? 15 : (VAR == DR_VARIANT_MOVING ? 18 : 12);
+    constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
     constexpr int NQ = (64 * OD / 4 + 63) / 64;  // float4 rows-stores per lane and step
     // the hand-counted wait assumes NQ obs + 1 reward + 1 done store per phase
@@ -1407,14 +1351,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
                 const uint64_t s = io.a_step0 + (uint64_t)t;
                 uint32_t ak0 = io.a_k0, ak1 = io.a_k1;
                 asm volatile("" : "+s"(ak0), "+s"(ak1));
-                const u32x4 r = philox4x32_10(
-                    u32x4{(uint32_t)s, (uint32_t)(s >> 32), (uint32_t)gid,
-                          TAG_ACTION ^ (uint32_t)(gid >> 32)},
-                    ak0, ak1);
-                const float4 act = make_float4(io.a_lo + io.a_span * u01_f32(r.x),
-                                               io.a_lo + io.a_span * u01_f32(r.y),
-                                               io.a_lo + io.a_span * u01_f32(r.z),
-                                               io.a_lo + io.a_span * u01_f32(r.w));
+                const float4 act = action_of(s, gid, ak0, ak1, io.a_lo, io.a_span);
                 sh.act[t % kWsNA][p * 64 + lane] = act;
                 if (io.act_out && live)
                     st_out(at(reinterpret_cast<float4 *>(io.act_out) + (int64_t)t * n_, i), act);
@@ -1652,10 +1589,10 @@ struct AbLds {
     S psi[2][kWsEnvs];                    // the yaw itself
 };
 
-template <typename S, bool GEN>
+template <typename S>
 __global__ __launch_bounds__(kAbThreads) void env_rollout_ab_kernel(EnvView<S> v, RolloutIO io,
                                                                     FieldPtrs<S> fp) {
-    constexpr int OD = 15;
+    constexpr int OD = od_of<DR_VARIANT_GYM>();
     constexpr int NQ = (64 * OD / 4 + 63) / 64;
     constexpr int S_OPS = NQ + 2;
     static_assert(S_OPS + kWsAhead * (S_OPS + 1) <= 63, "the action-load wait count must fit vmcnt");
@@ -1674,29 +1611,17 @@ __global__ __launch_bounds__(kAbThreads) void env_rollout_ab_kernel(EnvView<S> v
 
     if (role == 2) {
         // ---------------- memory wave (env_rollout_ws_kernel's, stores two
-        // phases behind the translation wave, three output slots) ----------
+        // phases behind the translation wave, three output slots; actions
+        // only from HBM: launch_rollout says why the random policy stays on
+        // the warp-specialised kernel).  Kept as its own copy: as one
+        // function shared with that kernel it changed this kernel's device
+        // code ----------
         const int64_t nvalid = (n_ - wbase) < 64 ? (n_ - wbase) : 64;
         const bool full = nvalid == 64 && (((uintptr_t)io.obs) & 15) == 0 &&
                           ((n_ * OD) & 3) == 0;
         const float4 *acts = reinterpret_cast<const float4 *>(io.actions);
-        const uint64_t gid = (uint64_t)(v.env_id_offset + i);
         auto load_act = [&](int t) {
-            if constexpr (GEN) {
-                const uint64_t s = io.a_step0 + (uint64_t)t;
-                uint32_t ak0 = io.a_k0, ak1 = io.a_k1;
-                asm volatile("" : "+s"(ak0), "+s"(ak1));
-                const u32x4 r = philox4x32_10(
-                    u32x4{(uint32_t)s, (uint32_t)(s >> 32), (uint32_t)gid,
-                          TAG_ACTION ^ (uint32_t)(gid >> 32)},
-                    ak0, ak1);
-                const float4 act = make_float4(io.a_lo + io.a_span * u01_f32(r.x),
-                                               io.a_lo + io.a_span * u01_f32(r.y),
-                                               io.a_lo + io.a_span * u01_f32(r.z),
-                                               io.a_lo + io.a_span * u01_f32(r.w));
-                sh.act[t % kWsNA][ps] = act;
-                if (io.act_out && live)
-                    st_out(at(reinterpret_cast<float4 *>(io.act_out) + (int64_t)t * n_, i), act);
-            } else if (nvalid > 0) {
+            if (nvalid > 0) {
                 ws_glds16(at(acts + (int64_t)t * n_, i),
                           (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)
                               &sh.act[t % kWsNA][p * 64]);
@@ -1733,7 +1658,7 @@ __global__ __launch_bounds__(kAbThreads) void env_rollout_ab_kernel(EnvView<S> v
             }
         };
         for (int t = 0; t <= kWsAhead && t < K; ++t) load_act(t);
-        if (!GEN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // actions 0 .. D
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // actions 0 .. D
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // B_(-1)
         for (int t = 0; t < K; ++t) {
             if (t + kWsAhead + 1 < K) load_act(t + kWsAhead + 1);
@@ -1742,7 +1667,7 @@ __global__ __launch_bounds__(kAbThreads) void env_rollout_ab_kernel(EnvView<S> v
             // younger in the steady state (q >= 2, loads through phase t):
             // q's S_OPS stores and D phases of one load and S_OPS stores;
             // otherwise at least this phase's S_OPS stores (t >= D >= 2).
-            if (!GEN && t + 1 < K && t + 1 > kWsAhead) {
+            if (t + 1 < K && t + 1 > kWsAhead) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (!full)
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2171,12 +2096,7 @@ __global__ __launch_bounds__(kBlock) void random_actions_kernel(
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const uint64_t gid = (uint64_t)(env_off + i);
-    const u32x4 r = philox4x32_10(
-        u32x4{(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)gid,
-              TAG_ACTION ^ (uint32_t)(gid >> 32)},
-        k0, k1);
-    out[i] = make_float4(lo + span * u01_f32(r.x), lo + span * u01_f32(r.y),
-                         lo + span * u01_f32(r.z), lo + span * u01_f32(r.w));
+    out[i] = action_of(step, gid, k0, k1, lo, span);
 }
 
 }  // namespace
@@ -2256,7 +2176,38 @@ size_t state_bytes(int64_t stride, int dtype, int variant) {
     return (size_t)F_N * stride * s + (size_t)stride * (8 + 4 + 4 + 4 + 4 + mot);
 }
 
+template <typename S>
+FieldPtrs<S> field_ptrs_of(const EnvView<S> &v) {
+    FieldPtrs<S> fp;
+    for (int k = 0; k < F_N; ++k) fp.p[k] = v.field(k);
+    fp.step = v.step;
+    fp.ep_num = v.ep_num;
+    fp.eps = v.eps;
+    return fp;
+}
+
 inline hipStream_t as_stream(void *s) { return static_cast<hipStream_t>(s); }
+
+// The handle's state scalar and variant as compile-time values:
+// f(TypeTag<S>{}, std::integral_constant<int, VAR>{}) for the handle's pair.
+template <typename T>
+struct TypeTag {
+    using type = T;
+};
+template <typename F>
+int with_state(const dr_handle *h, F &&f) {
+    auto by_variant = [&](auto s) {
+        switch (h->cfg.variant) {
+            case DR_VARIANT_GYM: return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
+            case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
+            case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
+            case DR_VARIANT_TAG: return f(s, std::integral_constant<int, DR_VARIANT_TAG>{});
+            default: return f(s, std::integral_constant<int, DR_VARIANT_VECTORIZED>{});
+        }
+    };
+    return h->cfg.state_dtype == DR_STATE_F64 ? by_variant(TypeTag<double>{})
+                                              : by_variant(TypeTag<float>{});
+}
 
 // The variant's trailing kernel argument (empty but for the smooth and tag
 // variants).
@@ -2281,46 +2232,31 @@ int launch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
 
 int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
                    int init, hipStream_t st) {
-    const bool f64 = h->cfg.state_dtype == DR_STATE_F64;
-    if (h->cfg.variant == DR_VARIANT_GYM)
-        return f64 ? launch_reset<double, DR_VARIANT_GYM>(h, mask, obs, mode, init, st)
-                   : launch_reset<float, DR_VARIANT_GYM>(h, mask, obs, mode, init, st);
-    if (h->cfg.variant == DR_VARIANT_MOVING)
-        return f64 ? launch_reset<double, DR_VARIANT_MOVING>(h, mask, obs, mode, init, st)
-                   : launch_reset<float, DR_VARIANT_MOVING>(h, mask, obs, mode, init, st);
-    if (h->cfg.variant == DR_VARIANT_SMOOTH)
-        return f64 ? launch_reset<double, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st)
-                   : launch_reset<float, DR_VARIANT_SMOOTH>(h, mask, obs, mode, init, st);
-    if (h->cfg.variant == DR_VARIANT_TAG)
-        return f64 ? launch_reset<double, DR_VARIANT_TAG>(h, mask, obs, mode, init, st)
-                   : launch_reset<float, DR_VARIANT_TAG>(h, mask, obs, mode, init, st);
-    return f64 ? launch_reset<double, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st)
-               : launch_reset<float, DR_VARIANT_VECTORIZED>(h, mask, obs, mode, init, st);
+    return with_state(h, [&](auto s, auto var) {
+        return launch_reset<typename decltype(s)::type, decltype(var)::value>(h, mask, obs, mode,
+                                                                              init, st);
+    });
 }
 
 template <typename S, int VAR, bool MON>
 int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
     EnvView<S> v = view_of<S>(h);
-    FieldPtrs<S> fp;
-    for (int k = 0; k < F_N; ++k) fp.p[k] = v.field(k);
-    fp.step = v.step;
-    fp.ep_num = v.ep_num;
-    fp.eps = v.eps;
+    const FieldPtrs<S> fp = field_ptrs_of(v);
     const VarArgs<VAR> va = var_args<VAR>(h);
     bool launched = false;
     if (!launched && VAR != DR_VARIANT_VECTORIZED && v.host_u) {   // parity mode
         if (h->rpw == 32)
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, true, false>),
-                               dim3(grid_for(h->n, DR_ENV_WPB * 32)), dim3(kEnvBlock), 0, st,
+                               dim3(grid_for(h->n, kEnvWpb * 32)), dim3(kEnvBlock), 0, st,
                                v, io, fp, va);
         else
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 64, true, false>),
-                               dim3(grid_for(h->n, DR_ENV_WPB * 64)), dim3(kEnvBlock), 0, st,
+                               dim3(grid_for(h->n, kEnvWpb * 64)), dim3(kEnvBlock), 0, st,
                                v, io, fp, va);
         launched = true;
     }
     if (!launched) {
-        const dim3 g64(grid_for(h->n, DR_ENV_WPB * 64)), g32(grid_for(h->n, DR_ENV_WPB * 32));
+        const dim3 g64(grid_for(h->n, kEnvWpb * 64)), g32(grid_for(h->n, kEnvWpb * 32));
         switch (h->rpw * 2 + (int)h->nt_loads) {
             case 64:
                 hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, false, false>), g32,
@@ -2347,32 +2283,16 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
 
 template <bool MON>
 int dispatch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
-    const bool f64 = h->cfg.state_dtype == DR_STATE_F64;
-    if (h->cfg.variant == DR_VARIANT_GYM)
-        return f64 ? launch_step<double, DR_VARIANT_GYM, MON>(h, io, st)
-                   : launch_step<float, DR_VARIANT_GYM, MON>(h, io, st);
-    if (h->cfg.variant == DR_VARIANT_MOVING)
-        return f64 ? launch_step<double, DR_VARIANT_MOVING, MON>(h, io, st)
-                   : launch_step<float, DR_VARIANT_MOVING, MON>(h, io, st);
-    if (h->cfg.variant == DR_VARIANT_SMOOTH)
-        return f64 ? launch_step<double, DR_VARIANT_SMOOTH, MON>(h, io, st)
-                   : launch_step<float, DR_VARIANT_SMOOTH, MON>(h, io, st);
-    if (h->cfg.variant == DR_VARIANT_TAG)
-        return f64 ? launch_step<double, DR_VARIANT_TAG, MON>(h, io, st)
-                   : launch_step<float, DR_VARIANT_TAG, MON>(h, io, st);
-    return f64 ? launch_step<double, DR_VARIANT_VECTORIZED, MON>(h, io, st)
-               : launch_step<float, DR_VARIANT_VECTORIZED, MON>(h, io, st);
+    return with_state(h, [&](auto s, auto var) {
+        return launch_step<typename decltype(s)::type, decltype(var)::value, MON>(h, io, st);
+    });
 }
 
 template <typename S, int VAR, bool GEN>
 int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t e0,
                    hipEvent_t e1) {
     EnvView<S> v = view_of<S>(h);
-    FieldPtrs<S> fp;
-    for (int k = 0; k < F_N; ++k) fp.p[k] = v.field(k);
-    fp.step = v.step;
-    fp.ep_num = v.ep_num;
-    fp.eps = v.eps;
+    const FieldPtrs<S> fp = field_ptrs_of(v);
     // The warp-specialised form while its grid is at most one block per CU
     // (n <= 256 x CUs: 65,536 envs on MI355X), where one physics wave per
     // SIMD has nothing else to overlap with; above that the one-role kernel
@@ -2405,11 +2325,10 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
             // form)
             const dim3 grid(grid_for(h->n, kWsEnvs)), block(kAbThreads);
             if (e0 || e1)
-                hipExtLaunchKernelGGL((env_rollout_ab_kernel<S, GEN>), grid, block, 0, st, e0,
-                                      e1, 0, v, io, fp);
+                hipExtLaunchKernelGGL((env_rollout_ab_kernel<S>), grid, block, 0, st, e0, e1, 0,
+                                      v, io, fp);
             else
-                hipLaunchKernelGGL((env_rollout_ab_kernel<S, GEN>), grid, block, 0, st, v, io,
-                                   fp);
+                hipLaunchKernelGGL((env_rollout_ab_kernel<S>), grid, block, 0, st, v, io, fp);
         } else {
             const dim3 grid(grid_for(h->n, kWsEnvs)), block(kWsThreads);
             if (e0 || e1)
@@ -2420,7 +2339,7 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
                                    io, fp);
         }
     } else {
-        const dim3 grid(grid_for(h->n, DR_ENV_WPB * 64)), block(kEnvBlock);
+        const dim3 grid(grid_for(h->n, kEnvWpb * 64)), block(kEnvBlock);
         if (e0 || e1)
             hipExtLaunchKernelGGL((env_rollout_kernel<S, VAR, 64, GEN>), grid, block, 0, st, e0,
                                   e1, 0, v, io, fp, var_args<VAR>(h));
@@ -2437,21 +2356,10 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
 template <bool GEN>
 int dispatch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t e0,
                      hipEvent_t e1) {
-    const bool f64 = h->cfg.state_dtype == DR_STATE_F64;
-    if (h->cfg.variant == DR_VARIANT_GYM)
-        return f64 ? launch_rollout<double, DR_VARIANT_GYM, GEN>(h, io, st, e0, e1)
-                   : launch_rollout<float, DR_VARIANT_GYM, GEN>(h, io, st, e0, e1);
-    if (h->cfg.variant == DR_VARIANT_MOVING)
-        return f64 ? launch_rollout<double, DR_VARIANT_MOVING, GEN>(h, io, st, e0, e1)
-                   : launch_rollout<float, DR_VARIANT_MOVING, GEN>(h, io, st, e0, e1);
-    if (h->cfg.variant == DR_VARIANT_SMOOTH)
-        return f64 ? launch_rollout<double, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1)
-                   : launch_rollout<float, DR_VARIANT_SMOOTH, GEN>(h, io, st, e0, e1);
-    if (h->cfg.variant == DR_VARIANT_TAG)
-        return f64 ? launch_rollout<double, DR_VARIANT_TAG, GEN>(h, io, st, e0, e1)
-                   : launch_rollout<float, DR_VARIANT_TAG, GEN>(h, io, st, e0, e1);
-    return f64 ? launch_rollout<double, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1)
-               : launch_rollout<float, DR_VARIANT_VECTORIZED, GEN>(h, io, st, e0, e1);
+    return with_state(h, [&](auto s, auto var) {
+        return launch_rollout<typename decltype(s)::type, decltype(var)::value, GEN>(h, io, st, e0,
+                                                                                     e1);
+    });
 }
 
 // DR_FIELD_MOTOR of dr_get_state / dr_gather_state / dr_set_state.
@@ -2523,9 +2431,10 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     h->cfg = cfg;
     h->n = cfg.num_envs;
     // SoA arrays are `stride` elements apart.  A pure power-of-two spacing
-    // would put the 17 concurrently streamed arrays at congruent addresses
-    // (same HBM channel bits); DR_STRIDE_PAD elements of skew break that.
-    h->stride = (cfg.num_envs + 63) / 64 * 64 + DR_STRIDE_PAD;
+    // puts the 17 concurrently streamed arrays at congruent addresses (same
+    // HBM channel bits); a stride padded to skew them was an A/B build that
+    // never became the default.
+    h->stride = (cfg.num_envs + 63) / 64 * 64;
     h->obs_dim = cfg.variant == DR_VARIANT_GYM
                      ? 15
                      : (cfg.variant == DR_VARIANT_MOVING

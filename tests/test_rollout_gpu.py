@@ -110,6 +110,62 @@ def test_rollout_random_policy_matches_random_actions():
     assert torch.equal(obs, o3) and torch.equal(rew, r3) and torch.equal(done, d3)
 
 
+@pytest.mark.parametrize("variant,dtype", [
+    ("gym", torch.float64),
+    ("moving", torch.float64),
+    ("vectorized", torch.float32),
+])
+def test_rollout_random_policy_small_ragged_with_resets(variant, dtype):
+    """The in-kernel random policy on the form the size rule picks at n = 321
+    (warp-specialised): one full 256-env block, then a block with one full
+    wave, one wave of a single env and two waves with no live env.  K = 19
+    crosses two kResetAhead group boundaries and exceeds kWsAhead + 2 phases.
+    max_steps = 6 makes every env hit the time limit at least three times; a
+    third of the envs start at step 4, so they reset at t = 1 and t = 7, twice
+    within one draw-ahead group: the drawn-ahead reset and the draw inside the
+    reset branch both run, deterministically."""
+    from drone_rl_amd import random_actions
+    n, K, seed, step0 = 321, 19, 2024, 700
+    reset_variant = variant != "vectorized"
+    a, b = _pair(n, variant, dtype, max_steps=6 if reset_variant else None)
+    if reset_variant:
+        for x in (a, b):
+            s = x.get("current_step").cpu()
+            s[::3] = 4
+            x.set("current_step", s)
+    got = torch.empty(K, n, 4, device="cuda")
+    obs, rew, done = a.rollout(K, None, seed=seed, step0=step0, actions_out=got)
+    acts = torch.empty(K, n, 4, device="cuda")
+    for t in range(K):
+        random_actions(n, seed=seed, step=step0 + t, env_id_offset=3 * n, out=acts[t])
+    assert torch.equal(got, acts)
+    for t in range(K):
+        so, sr, sd = b.step(acts[t])
+        assert torch.equal(obs[t], so), (t, "obs")
+        assert torch.equal(rew[t], sr), (t, "rew")
+        assert torch.equal(done[t], sd), (t, "done")
+    fa, fb = _fields(a), _fields(b)
+    for k in fa:
+        assert torch.equal(fa[k], fb[k]), k
+    if reset_variant:
+        assert int(done.sum()) >= 3 * n
+
+
+def test_rollout_random_policy_one_role_form_forced():
+    """The same check for (moving, f64) on the one-role kernel, which the size
+    rule does not pick at n = 321 (DRONERL_ROLLOUT_WS=0, in a subprocess)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, DRONERL_ROLLOUT_WS="0", PYTHONPATH=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "rollout_form_worker.py"),
+                        "moving", "321", "19", "6"], env=env, capture_output=True, text=True,
+                       timeout=100)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "ok" in r.stdout
+
+
 def test_rollout_last_step_vs_oracle():
     """65,536 f64 envs: 15 rollout steps, then one more rollout step checked
     on a subset against the CPU oracle (cref.gym_step, pinned to the
