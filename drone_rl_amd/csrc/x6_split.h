@@ -4,6 +4,16 @@
 // used by the weight-image split, the weight-gradient GEMM's operands and the
 // fused first-layer backward's grad_z1 / observation planes (gemm_x6.hip),
 // and the operand images below (also built by ppo_kernels.hip).
+//
+// Range of the exactness (tests/test_gemm_x6_schedule_gpu.py, designed
+// values): the split is exact for every finite x up to 0x7f7f7fff (above it
+// h rounds to inf) whose last set bit is at or above 2^-133, the smallest
+// bf16 denormal.  Measured on gfx950 under the library's build flags, both
+// v_cvt_pk_bf16_f32 and the f32 subtractions keep denormals (gradual
+// underflow, bitwise the IEEE result, inputs and outputs): an f32 denormal or
+// a remainder below 2^-126 is rounded to the bf16 denormal grid, so the
+// worst loss is 2^-134 absolute (4.6e-41).  Nothing is flushed, and the
+// values of a training run are nowhere near that range.
 #pragma once
 
 #include <cstdint>
@@ -61,7 +71,8 @@ __host__ __device__ inline int64_t wimg_off(int n, int k0) {
 }
 
 // Item t (b, n, 8-k chunk) of the weight image; transpose 2 builds both forms
-// (y 0: the W^T form at img, y 1: the W form after it).
+// (y 0: the transpose-0 image, Bt = W for z = h W^T, at img; y 1: the
+// transpose-1 image, Bt = W^T for grad_h = grad_z W, after it).
 __device__ inline void split_weights_item(const float *__restrict__ w, int transpose, int batch,
                                           uint8_t *__restrict__ img, int t, int y) {
     if (t >= batch * XN * (XK / 8)) return;

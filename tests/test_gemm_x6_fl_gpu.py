@@ -12,27 +12,18 @@ import torch
 
 from drone_rl_amd import _lib
 from drone_rl_amd._lib import check, ptr
+from x6_cases import level1_groups
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 
 
-def _align(x):
-    return (x + 255) & ~255
-
-
 def _level1_total(ws, m, nets=2, k=15, n=256):
     """Sum over the ng level-1 groups the first-layer workspace holds (the
-    dr_first_layer_backward2(defer = 1) layout) -> (dW (nets, n, k), db
-    (nets, n)) in f64."""
-    nb = min(-(-m // 16), 256)
-    P = nets * (k + 1) * n
-    gsize = -(-nb // 16)
-    ng = -(-nb // gsize)
-    off = _align(4 * nb * P) // 4
-    part2 = ws.view(torch.float32)[off:off + ng * P].double().cpu().view(ng, nets, k + 1, n)
-    tot = part2.sum(0)
+    dr_first_layer_backward2(defer = 1) layout, decoded by
+    x6_cases.level1_groups) -> (dW (nets, n, k), db (nets, n)) in f64."""
+    tot = level1_groups(ws, m, nets, k, n).cpu().sum(0)
     return tot[:, :k, :].transpose(1, 2).numpy(), tot[:, k, :].numpy()
 
 
