@@ -29,6 +29,7 @@ DR_VARIANT_VECTORIZED = 1
 DR_VARIANT_MOVING = 2
 DR_VARIANT_SMOOTH = 3
 DR_VARIANT_TAG = 4
+DR_VARIANT_RK4 = 5
 DR_STATE_F64 = 0
 DR_STATE_F32 = 1
 DR_RNG_PHILOX = 0
@@ -36,7 +37,7 @@ DR_RNG_HOST_UNIFORMS = 1
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
-          "ep_length": 9, "motion": 10, "motor": 11}
+          "ep_length": 9, "motion": 10, "motor": 11, "quat": 12}
 
 
 class dr_config(ctypes.Structure):

@@ -11,6 +11,9 @@
 // motor-force arrays and 4 obs floats (DESIGN.md sections 11 and 14).  The tag
 // variant couples env 2j with env 2j+1 through in-register lane exchanges; its
 // obs has 19 floats and it keeps no state of its own.
+// The rk4 variant keeps a unit quaternion in place of the Euler angles (its
+// fourth word is one more array of S) and advances the state by one RK4 step;
+// its obs has 16 floats.
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -406,7 +409,9 @@ constexpr int od_of() {
                ? 15
                : (VAR == DR_VARIANT_MOVING
                       ? 18
-                      : ((VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG) ? 19 : 12));
+                      : ((VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG)
+                             ? 19
+                             : (VAR == DR_VARIANT_RK4 ? 16 : 12)));
 }
 // What a variant's kernels take beyond the shared arguments: nothing, or the
 // smooth / tag variant's two parameters.  A trailing kernel argument of its own, so
@@ -422,6 +427,13 @@ template <>
 struct VarArgs<DR_VARIANT_TAG> {
     float radius;  // tag radius R > 0
     float crash;   // crash penalty c >= 0
+};
+template <>
+struct VarArgs<DR_VARIANT_RK4> {
+    // dt / 6 formed on the host in the state scalar (one IEEE divide per
+    // handle instead of one per lane and step): f64 and f32 state
+    double h6d;
+    float h6f;
 };
 // the force every motor applies after a reset: f32(mass * g / 4)
 constexpr float kHover32 = (float)(kMass * kG / 4);
@@ -501,6 +513,17 @@ __device__ inline S tag_reward(const S st[F_N], const S pp[3], float radius, boo
 template <typename S, int VAR>
 __device__ inline void make_obs(const S st[F_N], float ob[od_of<VAR>()],
                                 const float *ext = nullptr) {
+    if constexpr (VAR == DR_VARIANT_RK4) {
+        // p, v, q = (a, b, c, d), omega, target - p; ext[0] = f32(d)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) ob[k] = (float)st[k];
+        ob[9] = ext[0];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ob[10 + k] = (float)st[F_OMG + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ob[13 + k] = (float)(st[F_TGT + k] - st[F_POS + k]);
+        return;
+    }
     // _get_obs: f32(concat(pos, vel, euler, omega[, target - pos]))  (79)
 #pragma unroll
     for (int k = 0; k < 12; ++k) ob[k] = (float)st[k];
@@ -623,6 +646,115 @@ __device__ inline S physics_step(S st[F_N], float4 act, S dt, bool &crash) {
     return physics_step_mixed<S, VAR>(st, motor_mix(act), dt, crash);
 }
 
+// ---- rk4 variant (DR_VARIANT_RK4) ----
+// The gym env's task on the state y = (p, v, q, omega), q = (a, b, c, d) =
+// (w, x, y, z) a unit quaternion body -> world, advanced by one classic RK4
+// step with the action held.  In the kernels' registers a, b, c sit where
+// the Euler angles do (st[F_EUL ..]) and d in a register of its own, `qd`;
+// in memory d is one more array of S behind the monitor counters
+// (Layout::mot).  Every operation is one correctly rounded IEEE operation in
+// the order tests/rk4_ref.py fixes; there is no trigonometric function and
+// no divide but the normalisation's.
+enum : int { Y_P = 0, Y_V = 3, Y_Q = 6, Y_W = 10, Y_N = 13 };
+
+// dy/dt at y under thrust T and torques tau.
+template <typename S>
+__device__ inline void rk4_deriv(const S y[Y_N], S T, const S tau[3], S k[Y_N]) {
+    const S rM = (S)1 / (S)kMass, rIx = (S)1 / (S)kIxx, rIy = (S)1 / (S)kIyy,
+            rIz = (S)1 / (S)kIzz;
+    const S a = y[Y_Q + 0], b = y[Y_Q + 1], c = y[Y_Q + 2], d = y[Y_Q + 3];
+    const S w0 = y[Y_W + 0], w1 = y[Y_W + 1], w2 = y[Y_W + 2];
+    // R(q) column 2: the thrust is body-z only
+    const S r02 = (S)2 * (b * d + a * c);
+    const S r12 = (S)2 * (c * d - a * b);
+    const S r22 = (S)1 - (S)2 * (b * b + c * c);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) k[Y_P + j] = y[Y_V + j];
+    k[Y_V + 0] = (r02 * T) * rM;
+    k[Y_V + 1] = (r12 * T) * rM;
+    k[Y_V + 2] = (S)(-kG) + (r22 * T) * rM;
+    // q' = q (x) (0, omega) / 2
+    k[Y_Q + 0] = (S)0.5 * (((-b * w0) - c * w1) - d * w2);
+    k[Y_Q + 1] = (S)0.5 * ((a * w0 + c * w2) - d * w1);
+    k[Y_Q + 2] = (S)0.5 * ((a * w1 - b * w2) + d * w0);
+    k[Y_Q + 3] = (S)0.5 * ((a * w2 + b * w1) - c * w0);
+    // the gym's angular dynamics (drone.py:135-139) with the reciprocals
+    k[Y_W + 0] = (tau[0] - ((S)(kIyy - kIzz) * w1) * w2) * rIx;
+    k[Y_W + 1] = (tau[1] - ((S)(kIzz - kIxx) * w0) * w2) * rIy;
+    k[Y_W + 2] = (tau[2] - ((S)(kIxx - kIyy) * w0) * w1) * rIz;
+}
+
+// One step on registers: st[0..8] = p, v, (a, b, c); qd = d; st[F_OMG ..] =
+// omega; st[F_TGT ..] = target.  h6 = dt / 6.  Returns the gym's reward on
+// the new position and sets `crash` as physics_step_mixed does.
+template <typename S>
+__device__ inline S rk4_step(S st[F_N], S &qd, MotorMix mx, S dt, S h6, bool &crash) {
+    const S T = (S)mx.thr;
+    const S tau[3] = {(S)kFactor * (S)mx.phi, (S)kFactor * (S)mx.theta,
+                      (S)(kKyaw32 * mx.psi)};
+    S y[Y_N], yt[Y_N], k[Y_N], s12[Y_N], s34[Y_N];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) y[j] = st[j];
+    y[Y_Q + 3] = qd;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) y[Y_W + j] = st[F_OMG + j];
+    const S h2 = dt * (S)0.5;
+    rk4_deriv(y, T, tau, k);                               // k1
+#pragma unroll
+    for (int j = 0; j < Y_N; ++j) {
+        s12[j] = k[j];
+        yt[j] = y[j] + h2 * k[j];
+    }
+    rk4_deriv(yt, T, tau, k);                              // k2
+#pragma unroll
+    for (int j = 0; j < Y_N; ++j) {
+        s12[j] = s12[j] + (S)2 * k[j];
+        yt[j] = y[j] + h2 * k[j];
+    }
+    rk4_deriv(yt, T, tau, k);                              // k3
+#pragma unroll
+    for (int j = 0; j < Y_N; ++j) {
+        s34[j] = (S)2 * k[j];
+        yt[j] = y[j] + dt * k[j];
+    }
+    rk4_deriv(yt, T, tau, k);                              // k4
+#pragma unroll
+    for (int j = 0; j < Y_N; ++j) y[j] = y[j] + h6 * (s12[j] + (s34[j] + k[j]));
+    // back onto the unit sphere: an IEEE sqrt and divide
+    const S qa = y[Y_Q + 0], qb = y[Y_Q + 1], qc = y[Y_Q + 2], qq = y[Y_Q + 3];
+    const S n2 = ((qa * qa + qb * qb) + qc * qc) + qq * qq;
+    const S rn = (S)1 / m_sqrt(n2);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) st[F_EUL + j] = y[Y_Q + j] * rn;
+    qd = qq * rn;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) st[j] = y[j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) st[F_OMG + j] = y[Y_W + j];
+    // reward and crash: the gym's, on the new position (physics_step_mixed)
+    const S dx = st[F_POS + 0] - st[F_TGT + 0];
+    const S dy = st[F_POS + 1] - st[F_TGT + 1];
+    const S dz = st[F_POS + 2] - st[F_TGT + 2];
+    const S dist = m_sqrt((dx * dx + dy * dy) + dz * dz);
+    S r = (S)0.01 * -dist;
+    if (dist < (S)0.05) r += (S)1;
+    const S px = st[F_POS + 0], py = st[F_POS + 1], pz = st[F_POS + 2];
+    const S pn2 = (px * px + py * py) + pz * pz;
+    crash = (pz < (S)0) || (pn2 > (S)2500);
+    return r;
+}
+template <typename S>
+__device__ inline S rk4_h6(const VarArgs<DR_VARIANT_RK4> &va) {
+    if constexpr (sizeof(S) == 8) return va.h6d;
+    else return va.h6f;
+}
+// after gym_reset_regs (which zeroes st[3..11]): q = (1, 0, 0, 0)
+template <typename S>
+__device__ inline void rk4_reset_quat(S st[F_N], S &qd) {
+    st[F_EUL] = (S)1;
+    qd = (S)0;
+}
+
 // Per-wave variant: each wave stages its own 64 rows (3,840 B) and writes
 // them out with no workgroup barrier, so a wave delayed by a reset or a late
 // load does not hold back the other three waves of its block.
@@ -708,7 +840,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // the gym's stored target and reset (the smooth variant is the gym env
     // behind a motor lag; the tag variant carries the gym's target unread)
     constexpr bool TAG = VAR == DR_VARIANT_TAG;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG;
+    // (and the rk4 variant, the gym's task on another state and integrator)
+    constexpr bool RK4 = VAR == DR_VARIANT_RK4;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
@@ -756,11 +890,18 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     float tx[7];
     const bool pursuer = (i & 1) == 0;
     const float sigma = pursuer ? 1.0f : -1.0f;
-    const float *const ext = TAG ? tx : (SMOOTH ? fm : tvel);   // the obs past the gym's 15
+    // rk4: the quaternion's fourth word (the first three sit in st[F_EUL ..])
+    // and its f32 for the obs
+    S qd = (S)0;
+    float qx[1] = {0.f};
+    S *const p_qd = reinterpret_cast<S *>(v.mot);
+    // the obs past the gym's 15
+    const float *const ext = TAG ? tx : (SMOOTH ? fm : (RK4 ? qx : tvel));
     if constexpr (SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
+    if constexpr (RK4) qd = ld_in<NTL>(at(p_qd, i));
     if constexpr (TAG) {
         // nothing in the step reads the stored target: a reset writes it
 #pragma unroll
@@ -812,6 +953,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     if constexpr (SMOOTH) {
         // the physics sees the lagged forces, not the command
         r = physics_step<S, VAR>(st, smooth_filter(act, fm, va.alpha, dev_sq), v.dt, crash);
+    } else if constexpr (RK4) {
+        r = rk4_step<S>(st, qd, motor_mix(act), v.dt, rk4_h6<S>(va), crash);
     } else {
         r = physics_step<S, VAR>(st, act, v.dt, crash);
     }
@@ -853,6 +996,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     asm volatile("" ::"v"(step), "v"(ep_old), "v"(eps_old), "v"(ret0), "v"(len0));
 #pragma unroll
     for (int k = 0; k < (TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
+    if constexpr (RK4) asm volatile("" ::"v"(qd));
     if (live) {
         st_out(at(io.rew, i), rf);
         st_out(at(io.done, i), (uint8_t)done);
@@ -870,6 +1014,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             if (io.term_obs) {
                 // tag: the partner's terminal state, exchanged before the branch
                 if constexpr (TAG) tag_ext(st, pp, pv, sigma, tx);
+                if constexpr (RK4) qx[0] = (float)qd;
                 make_obs<S, VAR>(st, ob, ext);
 #pragma unroll
                 for (int k = 0; k < OD; ++k) io.term_obs[i * OD + k] = ob[k];
@@ -877,6 +1022,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             step = 0;
             if constexpr (GYMSTATE) {
                 gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old);
+                if constexpr (RK4) rk4_reset_quat(st, qd);
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
                 if constexpr (SMOOTH) {
@@ -903,6 +1049,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     }
     // ONE observation pass over the post-reset state (the terminal obs is
     // formed inside the reset branch only when the caller keeps it)
+    if constexpr (RK4) qx[0] = (float)qd;
     make_obs<S, VAR>(st, ob, ext);
     if constexpr (MON) {
         if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !any_crash);
@@ -926,6 +1073,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
+        if constexpr (RK4) st_out(at(p_qd, i), qd);
     }
     DR_STAMP(4);
     if (!live) {
@@ -990,7 +1138,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     constexpr int OD = od_of<VAR>();
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
     constexpr bool TAG = VAR == DR_VARIANT_TAG;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG;
+    constexpr bool RK4 = VAR == DR_VARIANT_RK4;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
@@ -1014,11 +1163,17 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     float tx[7];
     const bool pursuer = (i & 1) == 0;
     const float sigma = pursuer ? 1.0f : -1.0f;
-    const float *const ext = TAG ? tx : (SMOOTH ? fm : tvel);
+    // rk4: the quaternion's fourth word, carried in a register over the
+    // launch like the rest of the state, and its f32 for the obs
+    S qd = (S)0;
+    float qx[1] = {0.f};
+    S *const p_qd = reinterpret_cast<S *>(v.mot);
+    const float *const ext = TAG ? tx : (SMOOTH ? fm : (RK4 ? qx : tvel));
     if constexpr (SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
+    if constexpr (RK4) qd = *at(p_qd, i);
     if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
@@ -1086,7 +1241,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         if constexpr (VAR == DR_VARIANT_MOVING)
             moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
         bool crash;
-        S r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
+        S r;
+        if constexpr (RK4) r = rk4_step<S>(st, qd, mx, v.dt, rk4_h6<S>(va), crash);
+        else r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
         bool done;
         S pp[3], pv[3];
@@ -1124,6 +1281,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 if constexpr (GYMSTATE) {
                     gym_reset_regs(vk, i, 0, st, ep_num, eps, nd_ok ? &nd[0] : nullptr);
                     nd_ok = false;
+                    if constexpr (RK4) rk4_reset_quat(st, qd);
                     if constexpr (SMOOTH) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) fm[k] = kHover32;
@@ -1144,6 +1302,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             if (__any(done && io.auto_reset)) tag_partner(st, pp, pv);
             tag_ext(st, pp, pv, sigma, tx);
         }
+        if constexpr (RK4) qx[0] = (float)qd;
         make_obs<S, VAR>(st, ob, ext);
         if (!live) {
 #pragma unroll
@@ -1187,6 +1346,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         asm volatile("" ::"v"(ep_num), "v"(eps), "v"(a), "v"(b), "v"(step));
 #pragma unroll
         for (int k = 0; k < F_N; ++k) asm volatile("" ::"v"(st[k]));
+        if constexpr (RK4) asm volatile("" ::"v"(qd));
         if constexpr (VAR == DR_VARIANT_MOVING) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(cen[k]));
@@ -1238,6 +1398,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
+        if constexpr (RK4) st_out(at(p_qd, i), qd);
         if (reset_any) {
             if constexpr (GYMSTATE) {
 #pragma unroll
@@ -1952,10 +2113,15 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
         }
         S st[F_N];
         float tvel[3] = {0.f, 0.f, 0.f};
+        S qd = (S)0;              // rk4: the quaternion's fourth word
         const bool doit = (mask == nullptr) || mask[i];
         if (doit) {
             if constexpr (VAR == DR_VARIANT_GYM) {
                 gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
+            } else if constexpr (VAR == DR_VARIANT_RK4) {
+                gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
+                rk4_reset_quat(st, qd);
+                reinterpret_cast<S *>(v.mot)[i] = qd;
             } else if constexpr (VAR == DR_VARIANT_SMOOTH) {
                 gym_reset_regs(v, i, mode, st, v.ep_num[i], v.eps[i]);
 #pragma unroll
@@ -1974,6 +2140,7 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
         } else {
 #pragma unroll
             for (int k = 0; k < F_N; ++k) st[k] = v.field(k)[i];
+            if constexpr (VAR == DR_VARIANT_RK4) qd = reinterpret_cast<S *>(v.mot)[i];
         }
         if constexpr (VAR == DR_VARIANT_MOVING) {
             // stored target = the centre; the obs sees the target at `step`
@@ -1988,6 +2155,9 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
 #pragma unroll
             for (int k = 0; k < 4; ++k) fm[k] = v.mot[k * v.stride + i];
             make_obs<S, VAR>(st, ob, fm);
+        } else if constexpr (VAR == DR_VARIANT_RK4) {
+            const float qx[1] = {(float)qd};
+            make_obs<S, VAR>(st, ob, qx);
         } else {
             make_obs<S, VAR>(st, ob, tvel);
         }
@@ -2090,6 +2260,24 @@ __global__ void motor_field_kernel(float *mot, int64_t stride, int64_t n, const 
     }
 }
 
+// DR_FIELD_QUAT (rk4 variant), a kernel of its own like DR_FIELD_MOTOR's:
+// row j of the (k,4) buffer `io`, in the state scalar, is read from (get: ids
+// null, env j; gather: env ids[j]) or written to (set) the attitude (w, x,
+// y, z): the three arrays at F_EUL and the one at `mot`.
+template <typename S>
+__global__ void quat_field_kernel(EnvView<S> v, const int32_t *ids, int64_t k, S *io, int set) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const int64_t i = ids ? (int64_t)ids[j] : j;
+    if (i < 0 || i >= v.n) return;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        S *p = (c < 3 ? v.field(F_EUL + c) : reinterpret_cast<S *>(v.mot)) + i;
+        if (set) *p = io[j * 4 + c];
+        else io[j * 4 + c] = *p;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void random_actions_kernel(
     int64_t n, uint32_t k0, uint32_t k1, int64_t env_off, uint64_t step,
     float lo, float span, float4 *out) {
@@ -2155,7 +2343,9 @@ EnvView<S> view_of(const dr_handle *h) {
     v.ep_num = reinterpret_cast<int32_t *>(m + Layout<S>::ep_num(sp));
     v.ep_ret = reinterpret_cast<float *>(m + Layout<S>::ep_ret(sp));
     v.ep_len = reinterpret_cast<int32_t *>(m + Layout<S>::ep_len(sp));
-    v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH)
+    // (rk4: one array of S there, the quaternion's fourth word)
+    v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH ||
+             h->cfg.variant == DR_VARIANT_RK4)
                 ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
                 : nullptr;
     v.n = h->n;
@@ -2172,7 +2362,9 @@ size_t state_bytes(int64_t stride, int dtype, int variant) {
     const size_t s = dtype == DR_STATE_F64 ? sizeof(double) : sizeof(float);
     const size_t mot = variant == DR_VARIANT_MOVING
                            ? 9 * sizeof(float)
-                           : (variant == DR_VARIANT_SMOOTH ? 4 * sizeof(float) : 0);
+                           : (variant == DR_VARIANT_SMOOTH
+                                  ? 4 * sizeof(float)
+                                  : (variant == DR_VARIANT_RK4 ? s : 0));
     return (size_t)F_N * stride * s + (size_t)stride * (8 + 4 + 4 + 4 + 4 + mot);
 }
 
@@ -2202,6 +2394,7 @@ int with_state(const dr_handle *h, F &&f) {
             case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
             case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
             case DR_VARIANT_TAG: return f(s, std::integral_constant<int, DR_VARIANT_TAG>{});
+            case DR_VARIANT_RK4: return f(s, std::integral_constant<int, DR_VARIANT_RK4>{});
             default: return f(s, std::integral_constant<int, DR_VARIANT_VECTORIZED>{});
         }
     };
@@ -2215,6 +2408,8 @@ template <int VAR>
 VarArgs<VAR> var_args(const dr_handle *h) {
     if constexpr (VAR == DR_VARIANT_SMOOTH) return VarArgs<VAR>{h->alpha, h->rate_penalty};
     else if constexpr (VAR == DR_VARIANT_TAG) return VarArgs<VAR>{h->tag_radius, h->crash_penalty};
+    else if constexpr (VAR == DR_VARIANT_RK4)
+        return VarArgs<VAR>{h->cfg.dt / 6.0, (float)h->cfg.dt / 6.0f};
     else return VarArgs<VAR>{};
 }
 
@@ -2304,10 +2499,11 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
         const char *r = std::getenv("DRONERL_ROLLOUT_WS");
         return r ? (std::atoi(r) != 0 ? 1 : 0) : -1;
     }();
-    // The smooth and tag variants have the one-role kernel only (the lag state
-    // and the partner exchange are not built into the warp-specialised
-    // forms), whatever the override says.
-    constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG;
+    // The smooth, tag and rk4 variants have the one-role kernel only (the lag
+    // state, the partner exchange and the quaternion step are not built into
+    // the warp-specialised forms), whatever the override says.
+    constexpr bool ONE_ROLE =
+        VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG || VAR == DR_VARIANT_RK4;
     const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
@@ -2380,6 +2576,35 @@ int motor_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, fl
     return DR_OK;
 }
 
+// DR_FIELD_QUAT of dr_get_state / dr_gather_state / dr_set_state.
+int quat_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, void *io, int set,
+               void *stream) {
+    if (h->cfg.variant != DR_VARIANT_RK4)
+        return fail(h, DR_ERR_INVALID, std::string(who) + ": quat exists only for DR_VARIANT_RK4");
+    if (k == 0) return DR_OK;
+    DeviceGuard g(h->cfg.device);
+    if (h->cfg.state_dtype == DR_STATE_F64)
+        hipLaunchKernelGGL(quat_field_kernel<double>, dim3(grid_for(k)), dim3(kBlock), 0,
+                           as_stream(stream), view_of<double>(h), ids, k,
+                           static_cast<double *>(io), set);
+    else
+        hipLaunchKernelGGL(quat_field_kernel<float>, dim3(grid_for(k)), dim3(kBlock), 0,
+                           as_stream(stream), view_of<float>(h), ids, k,
+                           static_cast<float *>(io), set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return DR_OK;
+}
+
+// The rk4 variant keeps a quaternion where the others keep Euler angles.
+int euler_refused(dr_handle *h, const char *who, int field) {
+    if (field == DR_FIELD_EULER && h->cfg.variant == DR_VARIANT_RK4)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    std::string(who) + ": DR_VARIANT_RK4 has no Euler angles; use DR_FIELD_QUAT");
+    return DR_OK;
+}
+
 int check_rng(dr_handle *h) {
     if (h->cfg.rng_mode == DR_RNG_HOST_UNIFORMS && h->host_u == nullptr &&
         h->cfg.variant != DR_VARIANT_VECTORIZED)
@@ -2401,7 +2626,7 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     if (cfg.num_envs < 1) return fail(nullptr, DR_ERR_INVALID, "dr_create: num_envs must be >= 1");
     if (cfg.variant != DR_VARIANT_GYM && cfg.variant != DR_VARIANT_VECTORIZED &&
         cfg.variant != DR_VARIANT_MOVING && cfg.variant != DR_VARIANT_SMOOTH &&
-        cfg.variant != DR_VARIANT_TAG)
+        cfg.variant != DR_VARIANT_TAG && cfg.variant != DR_VARIANT_RK4)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown variant");
     if (cfg.state_dtype != DR_STATE_F64 && cfg.state_dtype != DR_STATE_F32)
         return fail(nullptr, DR_ERR_INVALID, "dr_create: unknown state_dtype");
@@ -2442,7 +2667,7 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
                             : ((cfg.variant == DR_VARIANT_SMOOTH ||
                                 cfg.variant == DR_VARIANT_TAG)
                                    ? 19
-                                   : 12));
+                                   : (cfg.variant == DR_VARIANT_RK4 ? 16 : 12)));
     // Launch form by batch size, from the measured sweep
     // (scripts/micro/ab_sweep.sh, profiles/r01_env_launch_sweep.txt):
     // [0, 384k) 64 rows/wave; [384k, 1.5M) 32 + nontemporal state loads;
@@ -2643,6 +2868,8 @@ int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (!out) return fail(h, DR_ERR_INVALID, "dr_get_state: out is null");
     if (field == DR_FIELD_MOTOR)
         return motor_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
+    if (field == DR_FIELD_QUAT) return quat_field(h, "dr_get_state", nullptr, h->n, out, 0, stream);
+    if (int rc = euler_refused(h, "dr_get_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)
@@ -2665,6 +2892,8 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
     if (!env_ids || !out || k < 0) return fail(h, DR_ERR_INVALID, "dr_gather_state: bad arguments");
     if (field == DR_FIELD_MOTOR)
         return motor_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
+    if (field == DR_FIELD_QUAT) return quat_field(h, "dr_gather_state", env_ids, k, out, 0, stream);
+    if (int rc = euler_refused(h, "dr_gather_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_gather_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)
@@ -2688,6 +2917,9 @@ int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     if (field == DR_FIELD_MOTOR)
         return motor_field(h, "dr_set_state", nullptr, h->n,
                            const_cast<float *>(static_cast<const float *>(in)), 1, stream);
+    if (field == DR_FIELD_QUAT)
+        return quat_field(h, "dr_set_state", nullptr, h->n, const_cast<void *>(in), 1, stream);
+    if (int rc = euler_refused(h, "dr_set_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
     if (field == DR_FIELD_MOTION && h->cfg.variant != DR_VARIANT_MOVING)

@@ -25,15 +25,15 @@ ARM_LENGTH = 0.5
 K_YAW = 0.01
 MAX_STEPS = 200
 MOTOR_MAX = 3 * MASS * G / 4.0          # 7.3575, action_space.high
-OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18, "smooth": 19, "tag": 19}
+OBS_DIM = {"gym": 15, "vectorized": 12, "moving": 18, "smooth": 19, "tag": 19, "rk4": 16}
 # the force each motor applies after a reset of the "smooth" variant
 # (DESIGN.md section 14): f32(mass * g / 4)
 HOVER = float(np.float32(MASS * G / 4.0))
 # reset uniforms per env and reset for rng="host" 
-RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14, "smooth": 5, "tag": 5}
+RESET_UNIFORMS = {"gym": 5, "vectorized": 5, "moving": 14, "smooth": 5, "tag": 5, "rk4": 5}
 _VARIANT_ID = {"gym": _lib.DR_VARIANT_GYM, "vectorized": _lib.DR_VARIANT_VECTORIZED,
                "moving": _lib.DR_VARIANT_MOVING, "smooth": _lib.DR_VARIANT_SMOOTH,
-               "tag": _lib.DR_VARIANT_TAG}
+               "tag": _lib.DR_VARIANT_TAG, "rk4": _lib.DR_VARIANT_RK4}
 # the "tag" variant's defaults
 TAG_RADIUS = 0.25
 CRASH_PENALTY = 0.0
@@ -41,6 +41,38 @@ CRASH_PENALTY = 0.0
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
 # (N, width) f32 fields a single variant owns
 _F32_ROW_FIELDS = {"motion": 9, "motor": 4}
+
+
+def quat_to_euler(q) -> np.ndarray:
+    """(..., 4) unit quaternions (w, x, y, z), body -> world, to the ZYX Euler
+    angles (roll, pitch, yaw) the other variants keep; f64.  Pitch comes back
+    in [-pi/2, pi/2]: the round trip holds for |pitch| < pi/2."""
+    q = np.asarray(q, np.float64)
+    a, b, c, d = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    roll = np.arctan2(2.0 * (a * b + c * d), 1.0 - 2.0 * (b * b + c * c))
+    pitch = np.arcsin(np.clip(2.0 * (a * c - d * b), -1.0, 1.0))
+    yaw = np.arctan2(2.0 * (a * d + b * c), 1.0 - 2.0 * (c * c + d * d))
+    return np.stack([roll, pitch, yaw], axis=-1)
+
+
+def euler_to_quat(e) -> np.ndarray:
+    """(..., 3) ZYX Euler angles (roll, pitch, yaw) to unit quaternions
+    (w, x, y, z); f64.  The inverse of quat_to_euler up to the sign of q."""
+    e = np.asarray(e, np.float64)
+    cr, sr = np.cos(e[..., 0] * 0.5), np.sin(e[..., 0] * 0.5)
+    cp, sp = np.cos(e[..., 1] * 0.5), np.sin(e[..., 1] * 0.5)
+    cy, sy = np.cos(e[..., 2] * 0.5), np.sin(e[..., 2] * 0.5)
+    return np.stack([cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy,
+                     cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy], axis=-1)
+
+
+def check_field(variant: str, field: str) -> None:
+    """The "quat" field exists only on the "rk4" variant (where "euler" is
+    derived from it on the host): raised as ValueError before any device
+    work.  ("motion" and "motor" on the wrong variant are refused by the C
+    call.)"""
+    if field == "quat" and variant != "rk4":
+        raise ValueError(f"field 'quat' exists only on variant 'rk4', not {variant!r}")
 
 
 def check_smoothing(variant: str, motor_alpha: float, rate_penalty: float) -> None:
@@ -94,6 +126,9 @@ class DroneBatch:
                or "tag" (envs 2j / 2j+1 are a pursuer / evader pair with a
                zero-sum reward; 19-d obs; num_envs
                counts drones and is even)
+               or "rk4" (the gym env's task on a unit-quaternion attitude
+               advanced by one RK4 step; 16-d obs; the
+               attitude is the field "quat", "euler" is derived from it)
     dtype      torch.float64 (reference precision) or torch.float32 state
     rng        "philox" (counter-based, seeded) or "host" (caller supplies
                the reset uniforms: numpy-MT19937 replay for parity tests)
@@ -334,9 +369,19 @@ class DroneBatch:
             return torch.empty(n, dtype=torch.float32, **where)
         if field in _F32_ROW_FIELDS:
             return torch.empty(n, _F32_ROW_FIELDS[field], dtype=torch.float32, **where)
+        if field == "quat":
+            return torch.empty(n, 4, dtype=self.dtype, **where)
         return torch.empty(n, dtype=torch.int32, **where)
 
+    def _derived_euler(self, field: str) -> bool:
+        """rk4 keeps no Euler angles: "euler" is converted from / to "quat"
+        on the host."""
+        check_field(self.variant, field)
+        return self.variant == "rk4" and field == "euler"
+
     def get(self, field: str) -> torch.Tensor:
+        if self._derived_euler(field):
+            return torch.from_numpy(quat_to_euler(self.get_host("quat"))).to(self.device)
         fid = _lib.FIELDS[field]
         out = self._field_out(field, device=self.device)
         check(self.L.dr_get_state(self.handle, fid, ptr(out), _stream(self.device)), self.handle)
@@ -345,6 +390,8 @@ class DroneBatch:
     def get_host(self, field: str) -> np.ndarray:
         """get(field) as a fresh numpy array: the field kernel writes into a
         pinned host buffer (one launch + one sync, no D2H copy)."""
+        if self._derived_euler(field):
+            return quat_to_euler(self.get_host("quat"))
         fid = _lib.FIELDS[field]
         bufs = self.__dict__.setdefault("_field_host", {})
         out = bufs.get(field)
@@ -357,9 +404,17 @@ class DroneBatch:
     def gather(self, field: str, env_ids: torch.Tensor, out: torch.Tensor | None = None):
         """`get(field)` for the envs in env_ids (int32 device tensor), into
         `out` if given (k,3) f64 / (k,) / (k,9) f32 for "motion" / (k,4) f32 for
-        "motor"."""
+        "motor" / (k,4) in the state dtype for "quat"."""
+        if self._derived_euler(field):
+            e = torch.from_numpy(quat_to_euler(self.gather("quat", env_ids).cpu().numpy()))
+            if out is None:
+                return e.to(self.device)
+            out.copy_(e)
+            return out
         fid = _lib.FIELDS[field]
         k = env_ids.numel()
+        if out is None and field == "quat":
+            out = torch.empty(k, 4, dtype=self.dtype, device=self.device)
         if out is None:
             if field in _VEC_FIELDS:
                 out = torch.empty(k, 3, dtype=torch.float64, device=self.device)
@@ -378,8 +433,13 @@ class DroneBatch:
         return out
 
     def set(self, field: str, value) -> None:
+        if self._derived_euler(field):
+            e = torch.as_tensor(value, dtype=torch.float64).reshape(self.num_envs, 3)
+            return self.set("quat", euler_to_quat(e.cpu().numpy()))
         fid = _lib.FIELDS[field]
-        if field in _VEC_FIELDS:
+        if field == "quat":
+            dt, shape = self.dtype, (self.num_envs, 4)
+        elif field in _VEC_FIELDS:
             dt, shape = torch.float64, (self.num_envs, 3)
         elif field == "eps":
             dt, shape = torch.float64, (self.num_envs,)

@@ -102,7 +102,9 @@ class PPOConfig:
     crash_penalty: float | None = None
 
     def __post_init__(self):
-        from .env import check_smoothing, check_tag
+        from .env import OBS_DIM, check_smoothing, check_tag
+        if self.variant not in OBS_DIM:
+            raise ValueError(f"unknown variant {self.variant!r}")
         check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
         check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
 
@@ -588,6 +590,9 @@ class PPOTrainer:
                    "ep_return", "ep_length")
 
     def _env_fields(self):
+        if self.cfg.variant == "rk4":
+            # the attitude is a quaternion ("euler" would be derived from it)
+            return tuple("quat" if k == "euler" else k for k in self._ENV_FIELDS)
         return self._ENV_FIELDS + {"moving": ("motion",),
                                    "smooth": ("motor",)}.get(self.cfg.variant, ())
 

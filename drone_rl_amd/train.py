@@ -61,10 +61,11 @@ def main(argv=None):
     ap.add_argument("--net", type=int, nargs="+", default=[256, 256])
     ap.add_argument("--state-dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag"], default="gym",
+    ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag", "rk4"], default="gym",
                     help="gym = DroneGymEnv; moving = the moving-target curriculum; "
                          "smooth = gym behind a motor lag with an action-rate penalty; "
-                         "tag = pursuer / evader pairs, self-play with one shared policy")
+                         "tag = pursuer / evader pairs, self-play with one shared policy; "
+                         "rk4 = the gym task on a quaternion attitude with an RK4 step")
     ap.add_argument("--tag-radius", type=float, default=None,
                     help="--variant tag: the pursuer's bonus radius in m (default 0.25)")
     ap.add_argument("--crash-penalty", type=float, default=None,

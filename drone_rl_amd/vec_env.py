@@ -34,8 +34,9 @@ try:  # optional: let SB3's isinstance(env, VecEnv) checks pass
 except Exception:  # noqa: BLE001 - SB3 absent (this image)
     _VecEnvBase = object
 
-# "motor": the smooth variant's motor forces (DroneBatch raises on the others)
-_STATE = ("pos", "vel", "euler", "omega", "target", "motor")
+# "motor": the smooth variant's motor forces; "quat": the rk4 variant's
+# attitude (DroneBatch raises on the others)
+_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat")
 _SCALAR = {"current_step": int, "ep_num": int, "eps": float}
 
 
@@ -126,6 +127,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
         idx = self._indices(indices)
         if attr_name == "motor" and self.batch.variant != "smooth":
             raise AttributeError("only the 'smooth' variant has attribute 'motor'")
+        if attr_name == "quat" and self.batch.variant != "rk4":
+            raise AttributeError("only the 'rk4' variant has attribute 'quat'")
         if attr_name in _STATE:
             v = self.batch.get_host(attr_name)
             return [v[i].copy() for i in idx]
@@ -181,7 +184,8 @@ class DroneVectorEnv:
     """gymnasium-1.x-style vector facade (same-step autoreset).
 
     reset(seed=None, options=None) -> (obs (N,15) f32, infos dict)
-    ((N,19) with variant="smooth": the gym obs plus the four motor forces)
+    ((N,19) with variant="smooth": the gym obs plus the four motor forces;
+    (N,16) with variant="rk4": the attitude is a quaternion)
     step(actions) -> (obs, rewards f32, terminated bool, truncated bool, infos)
 
     terminated/truncated follow the reference as shimmy converts it: the
@@ -200,8 +204,8 @@ class DroneVectorEnv:
                  dtype: torch.dtype = torch.float64, split_time_limit: bool = False,
                  as_tensors: bool = False, variant: str = "gym",
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0):
-        if variant not in ("gym", "smooth"):
-            raise ValueError("DroneVectorEnv wraps the 'gym' or 'smooth' variant")
+        if variant not in ("gym", "smooth", "rk4"):
+            raise ValueError("DroneVectorEnv wraps the 'gym', 'smooth' or 'rk4' variant")
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=True, keep_terminal_obs=True, monitor=True,
                                 motor_alpha=motor_alpha, rate_penalty=rate_penalty)

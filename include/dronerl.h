@@ -79,7 +79,19 @@ enum dr_variant {
        the gym env does.  obs (N,19) = the gym's first 12, partner - own
        position, partner - own velocity, the role.  tag_radius /
        crash_penalty: dr_set_tag (defaults 0.25, 0). */
-    DR_VARIANT_TAG = 4
+    DR_VARIANT_TAG = 4,
+    /* Quaternion attitude, RK4 integration (the opt-in non-parity mode; an
+       extension with no reference oracle, spec in DESIGN.md section 16): the
+       gym env's task -- reset draws, curriculum, reward, crash rule, step
+       limit, auto-reset, monitor -- on the state (p, v, unit quaternion q =
+       (w, x, y, z) body -> world, body rates omega).  The action is held over
+       the step; y = (p, v, q, omega) advances by one classic RK4 step of
+       p' = v, v' = R(q) e3 T / m - g e3, q' = q (x) (0, omega) / 2 and the
+       gym's angular dynamics, then q is normalised.  No trigonometric
+       function, no gimbal-lock singularity.  A reset sets q = (1, 0, 0, 0).
+       obs (N,16) = p, v, q, omega, target - p.  The attitude is
+       DR_FIELD_QUAT; DR_FIELD_EULER is refused (DR_ERR_UNSUPPORTED). */
+    DR_VARIANT_RK4 = 5
 };
 
 enum dr_state_dtype {
@@ -113,8 +125,11 @@ enum dr_field {   /* dr_get_state / dr_set_state, all device buffers      */
     DR_FIELD_EP_LENGTH = 9, /* (N,)  i32  running episode length (monitor)   */
     DR_FIELD_MOTION = 10,   /* (N,9) f32  moving variant: a xyz, w xyz, ph xyz
                                (DR_FIELD_TARGET is then the motion centre)  */
-    DR_FIELD_MOTOR = 11     /* (N,4) f32  smooth variant: the force each motor
+    DR_FIELD_MOTOR = 11,    /* (N,4) f32  smooth variant: the force each motor
                                applies (the lag filter's state)             */
+    DR_FIELD_QUAT = 12      /* (N,4) in the handle's state dtype (f64 or f32),
+                               rk4 variant: the attitude (w, x, y, z); a zero
+                               quaternion written here is the caller's error */
 };
 
 typedef struct dr_config {
@@ -150,7 +165,7 @@ int dr_create(const dr_config *cfg, dr_handle **out);
 int dr_destroy(dr_handle *h);
 
 int64_t dr_num_envs(const dr_handle *h);
-int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving, 19 smooth / tag */
+int dr_obs_dim(const dr_handle *h);   /* 15 gym, 12 vectorized, 18 moving, 19 smooth / tag, 16 rk4 */
 
 /* Reset every env and write (N,obs_dim) obs.  Replaces DroneEnv.reset
    (drone.py:48-75) called on each env by VecEnv.reset, and

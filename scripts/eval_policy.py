@@ -44,7 +44,9 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
     smooth = cfg.get("variant", "gym") == "smooth"
-    variant = "smooth" if smooth else "gym"
+    # "rk4"  is the gym's task: evaluated like it, on its
+    # own variant (16-d obs)
+    variant = "smooth" if smooth else ("rk4" if cfg.get("variant") == "rk4" else "gym")
     alpha = float(cfg.get("motor_alpha", 1.0)) if smooth else 1.0
     lam = float(cfg.get("rate_penalty", 0.0)) if smooth else 0.0
     pol = ActorCritic(OBS_DIM[variant], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)

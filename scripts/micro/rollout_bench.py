@@ -23,7 +23,7 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--dtype", default="f64")
 ap.add_argument("--act-sets", type=int, default=1,
                 help="distinct (k,N,4) action buffers cycled over the launches")
-ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag"], default="gym")
+ap.add_argument("--variant", choices=["gym", "moving", "smooth", "tag", "rk4"], default="gym")
 ap.add_argument("--tag-radius", type=float, default=None)
 ap.add_argument("--crash-penalty", type=float, default=None)
 ap.add_argument("--motor-alpha", type=float, default=1.0)
@@ -31,7 +31,8 @@ ap.add_argument("--rate-penalty", type=float, default=0.0)
 a = ap.parse_args()
 od = OBS_DIM[a.variant]
 # variant state beyond the gym's, read and written once per launch
-extra = {"gym": 0, "moving": 9 * 4, "smooth": 2 * 4 * 4, "tag": 0}[a.variant]
+extra = {"gym": 0, "moving": 9 * 4, "smooth": 2 * 4 * 4, "tag": 0,
+         "rk4": 2 * (8 if a.dtype == "f64" else 4)}[a.variant]
 kw = dict(motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty) if a.variant == "smooth" else {}
 if a.variant == "tag":
     kw = dict(tag_radius=a.tag_radius, crash_penalty=a.crash_penalty)
