@@ -3,6 +3,8 @@
 respect to SB3 itself).  Test infrastructure shared by the flagship-size
 parity test and the data-parallel union-gradient check
 (tests/test_ppo_flagship_parity_gpu.py, tests/dp_train_worker.py)."""
+import functools
+
 import numpy as np
 import torch
 
@@ -339,3 +341,196 @@ def f64_reference(sd, arch, obs, act, old_logp, adv, ret, clip, vf_coef, normali
                             A_raw.std().item() if many else float("nan")),
             })
     return tuple(out)
+
+
+# --------------------------------------------------------------------------
+# The rollout-side forward (PolicyInference, ActorCritic.forward): f64 with a
+# running fp32 bound, a plain fp32 restatement, the fixtures and the two-tier
+# check shared by tests/test_policy_forward_bound_cpu.py and
+# tests/test_policy_inference_f64_gpu.py.  Nothing here comes from the kernels.
+
+SHARP = 4.0     # margin of the sharp check: test_policy_forward_bound_cpu (b)
+
+
+def _net_layers(sd, arch, net, head):
+    """[(W, b)] of one MLP in f64: its hidden layers, then its head."""
+    names = [f"mlp_extractor.{net}.{2 * k}" for k in range(len(arch))] + [head]
+    return [(sd[f"{n}.weight"].double(), sd[f"{n}.bias"].double()) for n in names]
+
+
+_NETS = (("policy_net", "action_net"), ("value_net", "value_net"))
+
+
+def ulp32(x):
+    """Spacing of the f32 grid at |x| (f64 tensor in, f64 out; the normal
+    range's smallest spacing below it)."""
+    _, e = torch.frexp(torch.as_tensor(x, dtype=torch.float64).abs())
+    return torch.ldexp(torch.ones_like(e, dtype=torch.float64), (e - 24).clamp(min=-149))
+
+
+def forward_bound64(sd, arch, obs):
+    """(mean64 (m, 4), dmean, value64 (m,), dvalue): the f64 forward and, per
+    output entry, a bound on what ANY fp32 evaluation (every summation order,
+    fused or unfused multiply-adds, a tanh within TANH_ULP ulp) can differ
+    from it.  Per layer with input h, input error dh, K inputs and envelope
+    env = |h| |W|^T + |b|:
+
+        dz  = dh |W|^T + gamma(K + 2) (env + dh |W|^T)
+              the propagated input error, and K products + K - 1 sums + the
+              bias add (+ 1 spare) on the inputs as computed, |h^| <= |h| + dh
+        dh' = dz + 2 TANH_ULP u max(|tanh z|, 2^-126)
+              tanh is 1-Lipschitz; ulp(t) <= 2 u |t|
+
+    The x6 GEMM counts as an fp32 dot (tests/test_gemm_x6_gpu.py)."""
+    x = torch.as_tensor(obs).double()
+    out = []
+    for net, head in _NETS:
+        layers = _net_layers(sd, arch, net, head)
+        h, dh = x, torch.zeros_like(x)
+        for k, (W, b) in enumerate(layers):
+            aW = W.abs().T
+            prop = dh @ aW
+            dz = prop + gamma(W.shape[1] + 2) * (h.abs() @ aW + b.abs() + prop)
+            z = h @ W.T + b
+            if k == len(layers) - 1:
+                out += [z, dz]
+                break
+            h = torch.tanh(z)
+            dh = dz + 2 * TANH_ULP * U * h.abs().clamp(min=2.0 ** -126)
+    return out[0], out[1], out[2].flatten(), out[3].flatten()
+
+
+def forward32_cpu(sd, arch, obs, tanh_ulps=0, bf16_layer=None, generator=None):
+    """(mean (m, 4), value (m,)) by the plain fp32 restatement: torch's CPU
+    fp32 `@`, the bias added in fp32, tanh taken in f64 and rounded to f32.
+    Two deliberate defects for the margin / rejection tests: tanh_ulps moves
+    every tanh result by a uniform draw in +-tanh_ulps ulp (from `generator`);
+    bf16_layer rounds that layer's operands (its input and its weights;
+    hidden layers count from 0, the head is layer len(arch)) to bf16."""
+    x = torch.as_tensor(obs).float()
+    out = []
+    for net, head in _NETS:
+        layers = _net_layers(sd, arch, net, head)
+        h = x
+        for k, (W, b) in enumerate(layers):
+            W32 = W.float()
+            if bf16_layer == k:
+                h, W32 = h.bfloat16().float(), W32.bfloat16().float()
+            z = h @ W32.T + b.float()
+            if k == len(layers) - 1:
+                out.append(z)
+                break
+            h = torch.tanh(z.double()).float()
+            if tanh_ulps:
+                r = 2 * torch.rand(h.shape, generator=generator, dtype=torch.float64) - 1
+                h = (h.double() + tanh_ulps * r * ulp32(h.double())).float()
+    return out[0], out[1].flatten()
+
+
+def inference_fixture(obs_dim, arch, m, seed, scale):
+    """A policy and m observations for the rollout-side forward, all from one
+    torch.Generator: ActorCritic's init with flat *= scale, then flat += 0.05
+    randn -- every bias non-zero (action.b, value.b and the top layer's
+    included), outputs of rms 0.5-2 instead of a fresh init's 0.04; obs = 1.5
+    randn (f32) with row 0 all zeros and, when m >= 3, row 1 all 50.0 (the
+    position limit: the first layer saturates).  The parameters are drawn
+    before the observations, so m does not change the policy.
+    Returns dict(sd, arch, obs)."""
+    from drone_rl_amd.policy import ActorCritic
+    arch = tuple(arch)
+    g = torch.Generator().manual_seed(seed)
+    pol = ActorCritic(obs_dim, 4, arch, seed=seed, device="cpu")
+    with torch.no_grad():
+        pol.flat.mul_(scale)
+        pol.flat.add_(0.05 * torch.randn(pol.num_params, generator=g))
+    obs = 1.5 * torch.randn(m, obs_dim, generator=g)
+    obs[0] = 0.0
+    if m >= 3:
+        obs[1] = 50.0
+    return dict(sd=pol.state_dict(), arch=arch, obs=obs)
+
+
+# (id, obs_dim, arch, n, scale): every path of the rollout-side forward, each
+# at the smallest size that reaches it (the module docstring of
+# tests/test_policy_inference_f64_gpu.py says which)
+INFERENCE_CASES = [
+    ("x6_fused_images_128", 15, (256, 256), 128, 1.5),
+    ("x6_fused_images_384", 15, (256, 256), 384, 1.5),
+    ("x6_refresh", 19, (256, 256), 256, 1.5),
+    ("library_ragged", 15, (256, 256), 1000, 1.5),
+    ("one_env", 15, (64, 64), 1, 1.5),
+    ("unequal", 18, (64, 128), 257, 1.5),
+    ("depth1", 12, (128,), 255, 1.5),
+    ("depth3", 16, (64, 64, 64), 300, 1.5),
+    ("narrow_head", 32, (256, 252), 100, 1.5),
+    ("tiny", 4, (4,), 7, 1.5),
+    ("width_8", 8, (64, 64), 65, 1.5),
+    ("width_24", 24, (64, 64), 65, 1.5),
+    ("second_round", 15, (64, 64), 2053, 1.5),
+    ("saturated", 15, (256, 256), 384, 4.0),
+]
+INFERENCE_SEED = 11
+SMALL_N = 64            # below it the sharp check is per entry, against SMALL_REF_ROWS rows
+SMALL_REF_ROWS = 256
+
+
+def _errors(mean, value, mean64, value64):
+    """|out - f64| over all 5 m outputs as one (m, 5) f64 tensor."""
+    m = torch.as_tensor(mean).detach().cpu().double().reshape(mean64.shape)
+    v = torch.as_tensor(value).detach().cpu().double().reshape(value64.shape)
+    return torch.cat([(m - mean64).abs(), (v - value64).abs()[:, None]], 1)
+
+
+def inference_reference(sd, arch, obs):
+    """What check_inference needs of one (policy, observations) pair: the f64
+    outputs with their hard bound (forward_bound64 + one fp32 ulp of the
+    reference for the final store) and the plain restatement's rms / largest
+    error (forward32_cpu), the sharp check's yardstick."""
+    mean64, dmean, value64, dvalue = forward_bound64(sd, arch, obs)
+    ref = torch.cat([mean64, value64[:, None]], 1)
+    hard = torch.cat([dmean, dvalue[:, None]], 1) + ulp32(ref)
+    err32 = _errors(*forward32_cpu(sd, arch, obs), mean64, value64)
+    return dict(mean64=mean64, value64=value64, dmean=dmean, dvalue=dvalue, hard=hard,
+                ref_rms=err32.pow(2).mean().sqrt().item(), ref_max=err32.max().item(),
+                ref_hard=(err32 / hard).max().item(), n=obs.shape[0])
+
+
+@functools.lru_cache(maxsize=None)
+def inference_case(obs_dim, arch, n, scale, seed=INFERENCE_SEED):
+    """inference_fixture + inference_reference of one case, computed once per
+    process and shared (read-only) by every test that needs it.  Below
+    SMALL_N rows an rms says little, so `small_max` is the plain
+    restatement's largest error on the same policy's SMALL_REF_ROWS-row
+    fixture."""
+    fx = inference_fixture(obs_dim, arch, n, seed, scale)
+    fx.update(inference_reference(fx["sd"], fx["arch"], fx["obs"]))
+    if n < SMALL_N:
+        fx["small_max"] = inference_case(obs_dim, arch, SMALL_REF_ROWS, scale, seed)["ref_max"]
+    return fx
+
+
+def check_inference(ref, mean, value, rows=None):
+    """The two-tier criterion on outputs (mean, value) of the case `ref`
+    (inference_case / inference_reference), over all rows or `rows`:
+
+      hard   every entry within its fp32 bound: max error / bound <= 1
+      sharp  n >= SMALL_N: the rms error over all 5 n outputs <= SHARP x the
+             plain fp32 restatement's on the same fixture; below: every
+             entry's error <= SHARP x the restatement's largest on the same
+             policy's SMALL_REF_ROWS-row fixture
+
+    Returns dict(hard, sharp, hard_ok, sharp_ok): the two ratios (sharp
+    already divided by what it is compared with, so <= SHARP passes) and the
+    verdicts; a non-finite output fails both."""
+    err = _errors(mean, value, ref["mean64"], ref["value64"])
+    hard_b = ref["hard"]
+    if rows is not None:
+        err, hard_b = err[rows], hard_b[rows]
+    hard = (err / hard_b).max().item()
+    if "small_max" in ref:
+        sharp = err.max().item() / ref["small_max"]
+    else:
+        sharp = err.pow(2).mean().sqrt().item() / ref["ref_rms"]
+    finite = bool(torch.isfinite(err).all())
+    return dict(hard=hard, sharp=sharp, hard_ok=finite and hard <= 1.0,
+                sharp_ok=finite and sharp <= SHARP)

@@ -20,6 +20,7 @@ def _trainer(net_arch=(64, 64), **kw):
 
 
 def test_rollout_consistent_with_cpu():
+    """Derived fp32 bounds against f64, every network path: test_policy_inference_f64_gpu.py."""
     tr = _trainer()
     tr.collect_rollouts()
     T, N = tr.cfg.n_steps, tr.cfg.num_envs

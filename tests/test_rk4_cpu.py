@@ -296,7 +296,9 @@ def test_abi_refusals_before_any_device_call():
                              dt=0.02)
         h = ctypes.c_void_p()
         rc = L.dr_create(ctypes.byref(cfg), ctypes.byref(h))
-        msg = _lib.last_error()
+        # dr_last_error keeps the LAST error: after a call that succeeded it
+        # still holds an earlier call's message, which is not this call's
+        msg = _lib.last_error() if rc != _lib.DR_OK else ""
         if h.value:
             L.dr_destroy(h)
         return rc, msg
