@@ -13,7 +13,9 @@
 // obs has 19 floats and it keeps no state of its own.
 // The rk4 variant keeps a unit quaternion in place of the Euler angles (its
 // fourth word is one more array of S) and advances the state by one RK4 step;
-// its obs has 16 floats.
+// its obs has 16 floats.  A gym handle with wind
+// enabled (dr_set_wind) adds 6 f32 arrays, the mean wind and the gust, and no
+// obs float.
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -401,11 +403,16 @@ __device__ inline void moving_reset_regs(const EnvView<S> &v, int64_t i, int mod
     }
 }
 
+// The gym variant with wind enabled (dr_set_wind): a
+// kernel-variant tag of this file, not a public dr_variant value.  A gym
+// handle's kernels are instantiated on it once its wind arrays exist.
+constexpr int KVAR_WIND = 64;
+
 // ---- smooth-control variant (DR_VARIANT_SMOOTH) ----
 // Observation width of a variant.
 template <int VAR>
 constexpr int od_of() {
-    return VAR == DR_VARIANT_GYM
+    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND)
                ? 15
                : (VAR == DR_VARIANT_MOVING
                       ? 18
@@ -452,6 +459,49 @@ __device__ inline float4 smooth_filter(float4 a, float f[4], float alpha, float 
 #pragma unroll
     for (int j = 0; j < 4; ++j) f[j] = b * f[j] + alpha * c[j];
     return make_float4(f[0], f[1], f[2], f[3]);
+}
+
+// ---- wind, gusts and linear drag (dr_set_wind) ----
+// Per env six f32 words, the episode's mean wind m and the gust g, in six
+// arrays at EnvView::mot (the handle's second allocation, same stride).
+template <>
+struct VarArgs<KVAR_WIND> {
+    float k;   // linear drag per unit mass, 1/s
+    float b;   // gust persistence 1 - gust_rate
+    float c;   // gust noise scale sigma sqrt(3 (1 - b^2)), formed on the host
+    float W;   // bound of each axis of the mean wind; read by resets only
+};
+// f32(2u - 1) of a Philox word's 32-bit uniform: the subtraction is exact in
+// f64, the cast is the one rounding.
+__device__ inline float wind_pm1(uint32_t w) { return (float)(2.0 * u01_w32(w) - 1.0); }
+
+// The mean wind of env `gid` in episode `ep`: the reset stream's block 2.
+__device__ inline void wind_mean(uint32_t k0, uint32_t k1, uint64_t gid, int32_t ep, float W,
+                                 float m[3]) {
+    const u32x4 r = philox4x32_10(
+        u32x4{(uint32_t)ep, (uint32_t)gid, (uint32_t)(gid >> 32), TAG_RESET | 2u}, k0, k1);
+    m[0] = W * wind_pm1(r.x);
+    m[1] = W * wind_pm1(r.y);
+    m[2] = W * wind_pm1(r.z);
+}
+
+// The disturbance ahead of the gym step of an env at step counter `s` of
+// episode `ep`: the gust's AR(1) update, every operation one f32 rounding,
+// then the drag impulse on the velocity towards the air's, in S.  Always
+// drawn: at c == 0 the product c * xi is a zero whose sign is xi's.
+template <typename S>
+__device__ inline void wind_pre(S st[F_N], const float m[3], float g[3],
+                                const VarArgs<KVAR_WIND> &va, uint32_t k0, uint32_t k1,
+                                uint64_t gid, int32_t ep, int32_t s, S dt) {
+    const u32x4 r = philox4x32_10(
+        u32x4{(uint32_t)ep, (uint32_t)gid, (uint32_t)(gid >> 32), TAG_GUST | (uint32_t)s}, k0, k1);
+    const float xi[3] = {wind_pm1(r.x), wind_pm1(r.y), wind_pm1(r.z)};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        g[k] = va.b * g[k] + va.c * xi[k];
+        const S w = (S)(m[k] + g[k]);
+        st[F_VEL + k] = st[F_VEL + k] + ((S)va.k * (w - st[F_VEL + k])) * dt;
+    }
 }
 
 // ---- tag variant (DR_VARIANT_TAG) ----
@@ -842,7 +892,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     constexpr bool TAG = VAR == DR_VARIANT_TAG;
     // (and the rk4 variant, the gym's task on another state and integrator)
     constexpr bool RK4 = VAR == DR_VARIANT_RK4;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4;
+    // (and the gym env with wind, the gym's step behind a disturbance)
+    constexpr bool WIND = VAR == KVAR_WIND;
+    constexpr bool GYMSTATE =
+        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
@@ -902,6 +955,15 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
     if constexpr (RK4) qd = ld_in<NTL>(at(p_qd, i));
+    // wind: the episode's mean wind and the gust
+    float wm[3], wg[3];
+    if constexpr (WIND) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            wm[k] = *at(v.mot + k * v.stride, i);
+            wg[k] = *at(v.mot + (3 + k) * v.stride, i);
+        }
+    }
     if constexpr (TAG) {
         // nothing in the step reads the stored target: a reset writes it
 #pragma unroll
@@ -948,6 +1010,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
     }
 
+    // the gust and the drag impulse sit in front of the gym step, on the
+    // step counter and episode the step starts from
+    if constexpr (WIND)
+        wind_pre<S>(st, wm, wg, va, v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old,
+                    step, v.dt);
     bool crash;
     S r;
     if constexpr (SMOOTH) {
@@ -1023,6 +1090,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             if constexpr (GYMSTATE) {
                 gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old);
                 if constexpr (RK4) rk4_reset_quat(st, qd);
+                if constexpr (WIND) {
+                    // the new episode's mean wind (Philox in host-uniform
+                    // mode too), still air around it
+                    wind_mean(v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old + 1,
+                              va.W, wm);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) wg[k] = 0.f;
+                }
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
                 if constexpr (SMOOTH) {
@@ -1074,6 +1149,13 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
         if constexpr (RK4) st_out(at(p_qd, i), qd);
+        if constexpr (WIND) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                st_out(at(v.mot + k * v.stride, i), wm[k]);
+                st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
+            }
+        }
     }
     DR_STAMP(4);
     if (!live) {
@@ -1139,7 +1221,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
     constexpr bool TAG = VAR == DR_VARIANT_TAG;
     constexpr bool RK4 = VAR == DR_VARIANT_RK4;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4;
+    constexpr bool WIND = VAR == KVAR_WIND;
+    constexpr bool GYMSTATE =
+        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
@@ -1174,6 +1258,15 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
     if constexpr (RK4) qd = *at(p_qd, i);
+    // wind: the mean wind and the gust, carried in registers over the launch
+    float wm[3], wg[3];
+    if constexpr (WIND) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            wm[k] = *at(v.mot + k * v.stride, i);
+            wg[k] = *at(v.mot + (3 + k) * v.stride, i);
+        }
+    }
     if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
@@ -1240,6 +1333,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         }
         if constexpr (VAR == DR_VARIANT_MOVING)
             moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
+        if constexpr (WIND)
+            wind_pre<S>(st, wm, wg, va, vk.seed_lo, vk.seed_hi, gid, ep_num, step, v.dt);
         bool crash;
         S r;
         if constexpr (RK4) r = rk4_step<S>(st, qd, mx, v.dt, rk4_h6<S>(va), crash);
@@ -1285,6 +1380,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                     if constexpr (SMOOTH) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) fm[k] = kHover32;
+                    }
+                    if constexpr (WIND) {
+                        wind_mean(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va.W, wm);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                     }
                 } else {
                     moving_reset_regs(vk, i, 0, st, cen, mp, ep_num, eps, nd_ok ? nd : nullptr);
@@ -1357,6 +1457,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
             for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(fm[k]));
         }
+        if constexpr (WIND) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(wm[k]), "v"(wg[k]));
+        }
         // Two steps ahead, in two registers that alternate (the loop is
         // unrolled by two so each keeps its role): step t's action was
         // loaded at the top of step t-2; younger than that load are step
@@ -1399,6 +1503,13 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
         if constexpr (RK4) st_out(at(p_qd, i), qd);
+        if constexpr (WIND) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                st_out(at(v.mot + k * v.stride, i), wm[k]);
+                st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
+            }
+        }
         if (reset_any) {
             if constexpr (GYMSTATE) {
 #pragma unroll
@@ -2278,6 +2389,43 @@ __global__ void quat_field_kernel(EnvView<S> v, const int32_t *ids, int64_t k, S
     }
 }
 
+// Wind: the mean wind of each env's CURRENT episode (ep_num as stored) and a
+// zero gust, for every env (mask null: the enabling dr_set_wind, dr_reset) or
+// those with mask[i] != 0 (dr_reset_masked).  Runs behind the gym's
+// env_reset_kernel on the same stream, which has already counted the new
+// episode, so that kernel and its argument block stay the gym's.
+__global__ __launch_bounds__(kBlock) void wind_fill_kernel(float *wind, int64_t stride, int64_t n,
+                                                           const int32_t *ep_num,
+                                                           int64_t env_id_offset, uint32_t k0,
+                                                           uint32_t k1, float W,
+                                                           const uint8_t *mask) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (mask && !mask[i]) return;
+    float m[3];
+    wind_mean(k0, k1, (uint64_t)(env_id_offset + i), ep_num[i], W, m);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        wind[k * stride + i] = m[k];
+        wind[(3 + k) * stride + i] = 0.f;
+    }
+}
+
+// DR_FIELD_WIND, as motor_field_kernel: row j of the (k,6) f32 buffer `io`
+// (mean wind xyz, gust xyz) is read from or written to the six wind arrays.
+__global__ void wind_field_kernel(float *wind, int64_t stride, int64_t n, const int32_t *ids,
+                                  int64_t k, float *io, int set) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const int64_t i = ids ? (int64_t)ids[j] : j;
+    if (i < 0 || i >= n) return;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        if (set) wind[c * stride + i] = io[j * 6 + c];
+        else io[j * 6 + c] = wind[c * stride + i];
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void random_actions_kernel(
     int64_t n, uint32_t k0, uint32_t k1, int64_t env_off, uint64_t step,
     float lo, float span, float4 *out) {
@@ -2310,6 +2458,13 @@ struct dr_handle {
     // DR_VARIANT_TAG (dr_set_tag): passed to each launch
     float tag_radius = 0.25f;
     float crash_penalty = 0.0f;
+    // DR_VARIANT_GYM (dr_set_wind): the parameters as given, the two the host
+    // derives from them (b = 1 - gust_rate, c = sigma sqrt(3 (1 - b^2))), and
+    // the six f32 arrays of `stride` elements the first non-neutral call
+    // allocates; while null the handle launches the gym's kernels
+    float drag = 0.0f, wind_speed = 0.0f, gust_sigma = 0.0f, gust_rate = 0.0f;
+    float gust_b = 1.0f, gust_c = 0.0f;
+    float *wind = nullptr;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -2347,7 +2502,7 @@ EnvView<S> view_of(const dr_handle *h) {
     v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH ||
              h->cfg.variant == DR_VARIANT_RK4)
                 ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
-                : nullptr;
+                : (h->cfg.variant == DR_VARIANT_GYM ? h->wind : nullptr);
     v.n = h->n;
     v.env_id_offset = h->cfg.env_id_offset;
     v.host_u = h->host_u;
@@ -2390,7 +2545,10 @@ template <typename F>
 int with_state(const dr_handle *h, F &&f) {
     auto by_variant = [&](auto s) {
         switch (h->cfg.variant) {
-            case DR_VARIANT_GYM: return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
+            case DR_VARIANT_GYM:
+                // with wind enabled: the gym-with-wind kernels
+                if (h->wind) return f(s, std::integral_constant<int, KVAR_WIND>{});
+                return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
             case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
             case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
             case DR_VARIANT_TAG: return f(s, std::integral_constant<int, DR_VARIANT_TAG>{});
@@ -2410,6 +2568,8 @@ VarArgs<VAR> var_args(const dr_handle *h) {
     else if constexpr (VAR == DR_VARIANT_TAG) return VarArgs<VAR>{h->tag_radius, h->crash_penalty};
     else if constexpr (VAR == DR_VARIANT_RK4)
         return VarArgs<VAR>{h->cfg.dt / 6.0, (float)h->cfg.dt / 6.0f};
+    else if constexpr (VAR == KVAR_WIND)
+        return VarArgs<VAR>{h->drag, h->gust_b, h->gust_c, h->wind_speed};
     else return VarArgs<VAR>{};
 }
 
@@ -2425,11 +2585,32 @@ int launch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
     return DR_OK;
 }
 
+// The mean wind of every env's (mask: the masked envs') current episode and a
+// zero gust, enqueued on `st`.
+int launch_wind_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
+    const int32_t *ep_num = h->cfg.state_dtype == DR_STATE_F64 ? view_of<double>(h).ep_num
+                                                               : view_of<float>(h).ep_num;
+    hipLaunchKernelGGL(wind_fill_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->wind,
+                       h->stride, h->n, ep_num, h->cfg.env_id_offset, (uint32_t)h->cfg.seed,
+                       (uint32_t)(h->cfg.seed >> 32), h->wind_speed, mask);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string("wind_fill_kernel: ") + hipGetErrorString(e));
+    return DR_OK;
+}
+
 int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
                    int init, hipStream_t st) {
     return with_state(h, [&](auto s, auto var) {
-        return launch_reset<typename decltype(s)::type, decltype(var)::value>(h, mask, obs, mode,
-                                                                              init, st);
+        // a wind handle resets as the gym does (the wind is not observed),
+        // then draws the new episodes' mean wind behind it
+        constexpr int V = decltype(var)::value;
+        constexpr int RV = V == KVAR_WIND ? (int)DR_VARIANT_GYM : V;
+        int rc = launch_reset<typename decltype(s)::type, RV>(h, mask, obs, mode, init, st);
+        if constexpr (V == KVAR_WIND) {
+            if (rc == DR_OK) rc = launch_wind_fill(h, mask, st);
+        }
+        return rc;
     });
 }
 
@@ -2502,8 +2683,9 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
     // The smooth, tag and rk4 variants have the one-role kernel only (the lag
     // state, the partner exchange and the quaternion step are not built into
     // the warp-specialised forms), whatever the override says.
-    constexpr bool ONE_ROLE =
-        VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG || VAR == DR_VARIANT_RK4;
+    // (likewise a gym handle with wind: m and g ride in its registers)
+    constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG ||
+                              VAR == DR_VARIANT_RK4 || VAR == KVAR_WIND;
     const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
@@ -2591,6 +2773,22 @@ int quat_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, voi
         hipLaunchKernelGGL(quat_field_kernel<float>, dim3(grid_for(k)), dim3(kBlock), 0,
                            as_stream(stream), view_of<float>(h), ids, k,
                            static_cast<float *>(io), set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return DR_OK;
+}
+
+// DR_FIELD_WIND of dr_get_state / dr_gather_state / dr_set_state.
+int wind_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, float *io, int set,
+               void *stream) {
+    if (!h->wind)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    std::string(who) + ": wind exists only after a non-neutral dr_set_wind");
+    if (k == 0) return DR_OK;
+    DeviceGuard g(h->cfg.device);
+    hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
+                       h->wind, h->stride, h->n, ids, k, io, set);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -2726,6 +2924,7 @@ int dr_destroy(dr_handle *h) {
         // The caller's streams may still use the state: drain first.
         (void)hipDeviceSynchronize();
         (void)hipFree(h->mem);
+        if (h->wind) (void)hipFree(h->wind);
     }
     delete h;
     return DR_OK;
@@ -2869,6 +3068,8 @@ int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (field == DR_FIELD_MOTOR)
         return motor_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
     if (field == DR_FIELD_QUAT) return quat_field(h, "dr_get_state", nullptr, h->n, out, 0, stream);
+    if (field == DR_FIELD_WIND)
+        return wind_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
     if (int rc = euler_refused(h, "dr_get_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
@@ -2893,6 +3094,8 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
     if (field == DR_FIELD_MOTOR)
         return motor_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
     if (field == DR_FIELD_QUAT) return quat_field(h, "dr_gather_state", env_ids, k, out, 0, stream);
+    if (field == DR_FIELD_WIND)
+        return wind_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
     if (int rc = euler_refused(h, "dr_gather_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_gather_state: unknown field");
@@ -2919,6 +3122,9 @@ int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
                            const_cast<float *>(static_cast<const float *>(in)), 1, stream);
     if (field == DR_FIELD_QUAT)
         return quat_field(h, "dr_set_state", nullptr, h->n, const_cast<void *>(in), 1, stream);
+    if (field == DR_FIELD_WIND)
+        return wind_field(h, "dr_set_state", nullptr, h->n,
+                          const_cast<float *>(static_cast<const float *>(in)), 1, stream);
     if (int rc = euler_refused(h, "dr_set_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
@@ -2991,6 +3197,76 @@ int dr_get_tag(const dr_handle *h, float *tag_radius, float *crash_penalty) {
     if (h->cfg.variant != DR_VARIANT_TAG) return DR_ERR_UNSUPPORTED;
     if (tag_radius) *tag_radius = h->tag_radius;
     if (crash_penalty) *crash_penalty = h->crash_penalty;
+    return DR_OK;
+}
+
+int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma, float gust_rate) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_wind: null handle");
+    // written so that NaN fails every test
+    constexpr float kMax = 3.4028234663852886e38f;
+    if (!(drag >= 0.0f && drag <= kMax))
+        return fail(h, DR_ERR_INVALID, "dr_set_wind: drag must be finite and >= 0");
+    if (!(wind_speed >= 0.0f && wind_speed <= kMax))
+        return fail(h, DR_ERR_INVALID, "dr_set_wind: wind_speed must be finite and >= 0");
+    if (!(gust_sigma >= 0.0f && gust_sigma <= kMax))
+        return fail(h, DR_ERR_INVALID, "dr_set_wind: gust_sigma must be finite and >= 0");
+    if (!(gust_rate >= 0.0f && gust_rate <= 1.0f))
+        return fail(h, DR_ERR_INVALID, "dr_set_wind: gust_rate must be in [0, 1]");
+    // the explicit drag update must not overshoot the air's velocity
+    if (!((double)drag * h->cfg.dt <= 1.0))
+        return fail(h, DR_ERR_INVALID, "dr_set_wind: drag * dt must be <= 1");
+    if (h->cfg.variant != DR_VARIANT_GYM)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: only DR_VARIANT_GYM has wind");
+    // the gust counter carries the step counter in its low 24 bits
+    if (h->cfg.max_steps >= (1 << 24))
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: max_steps must be below 2^24");
+    const bool neutral =
+        drag == 0.0f && wind_speed == 0.0f && gust_sigma == 0.0f && gust_rate == 0.0f;
+    const bool enable = !h->wind && !neutral;
+    float *w = nullptr;
+    DeviceGuard g(h->cfg.device);
+    if (enable) {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&w), (size_t)6 * h->stride * sizeof(float));
+        if (e != hipSuccess)
+            return fail(h, DR_ERR_NOMEM,
+                        std::string("dr_set_wind: hipMalloc: ") + hipGetErrorString(e));
+    }
+    h->drag = drag;
+    h->wind_speed = wind_speed;
+    h->gust_sigma = gust_sigma;
+    h->gust_rate = gust_rate;
+    h->gust_b = 1.0f - gust_rate;
+    h->gust_c = (float)((double)gust_sigma *
+                        std::sqrt(3.0 * (1.0 - (double)h->gust_b * (double)h->gust_b)));
+    if (enable) {
+        // every env's current episode gets its mean wind now, so that it is
+        // a function of (key, env, episode) whenever wind was switched on;
+        // the state may have been written on any stream: drain, fill, drain
+        hipError_t e = hipDeviceSynchronize();
+        h->wind = w;
+        int rc = e == hipSuccess ? launch_wind_fill(h, nullptr, nullptr)
+                                 : fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        if (rc == DR_OK) {
+            e = hipDeviceSynchronize();
+            if (e != hipSuccess) rc = fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        }
+        if (rc != DR_OK) {
+            h->wind = nullptr;
+            (void)hipFree(w);
+            return rc;
+        }
+    }
+    return DR_OK;
+}
+
+int dr_get_wind(const dr_handle *h, float *drag, float *wind_speed, float *gust_sigma,
+                float *gust_rate) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_wind: null handle");
+    if (h->cfg.variant != DR_VARIANT_GYM) return DR_ERR_UNSUPPORTED;
+    if (drag) *drag = h->drag;
+    if (wind_speed) *wind_speed = h->wind_speed;
+    if (gust_sigma) *gust_sigma = h->gust_sigma;
+    if (gust_rate) *gust_rate = h->gust_rate;
     return DR_OK;
 }
 

@@ -40,7 +40,7 @@ CRASH_PENALTY = 0.0
 
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
 # (N, width) f32 fields a single variant owns
-_F32_ROW_FIELDS = {"motion": 9, "motor": 4}
+_F32_ROW_FIELDS = {"motion": 9, "motor": 4, "wind": 6}
 
 
 def quat_to_euler(q) -> np.ndarray:
@@ -86,6 +86,35 @@ def check_smoothing(variant: str, motor_alpha: float, rate_penalty: float) -> No
         raise ValueError(f"rate_penalty must be finite and >= 0, got {rate_penalty!r}")
     if variant != "smooth" and (a != 1.0 or lam != 0.0):
         raise ValueError(f"motor_alpha / rate_penalty need variant='smooth', not {variant!r}")
+
+
+def check_wind(variant: str, drag=0.0, wind_speed=0.0, gust_sigma=0.0, gust_rate=0.0,
+               max_steps: int | None = None) -> tuple[float, float, float, float]:
+    """The argument rules of dr_set_wind, raised as
+    ValueError before any device work: drag, wind_speed and gust_sigma finite
+    and >= 0 in f32, gust_rate in [0, 1], drag * dt <= 1 (the explicit drag
+    update must not overshoot), all four at 0 on every variant but "gym", and
+    a step limit below 2^24 where any is not.  Returns the four values as the
+    kernels see them (rounded to f32)."""
+    names = ("drag", "wind_speed", "gust_sigma", "gust_rate")
+    vals = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for name, x in zip(names, (drag, wind_speed, gust_sigma, gust_rate)):
+            v = float(np.float32(x))
+            if not (0.0 <= v < float("inf")):
+                raise ValueError(f"{name} must be finite and >= 0, got {x!r}")
+            vals.append(v)
+    if vals[3] > 1.0:
+        raise ValueError(f"gust_rate must be in [0, 1], got {gust_rate!r}")
+    if vals[0] * DT > 1.0:
+        raise ValueError(f"drag * dt must be <= 1 (dt = {DT}), got drag = {drag!r}")
+    if any(vals):
+        if variant != "gym":
+            raise ValueError("drag / wind_speed / gust_sigma / gust_rate need variant='gym', "
+                             f"not {variant!r}")
+        if max_steps is not None and int(max_steps) >= 1 << 24:
+            raise ValueError("wind needs max_steps below 2^24")
+    return tuple(vals)
 
 
 def check_tag(variant: str, tag_radius, crash_penalty, num_envs: int | None = None,
@@ -142,6 +171,14 @@ class DroneBatch:
                "tag" only: the distance inside which the pursuer collects its
                bonus (> 0) and what a crashing drone pays (>= 0).  None = the
                variant's defaults (0.25, 0).
+    drag, wind_speed, gust_sigma, gust_rate
+               "gym" only: linear drag per unit mass
+               (1/s), the bound of each axis of the per-episode mean wind
+               (m/s), the gusts' stationary standard deviation per axis (m/s)
+               and their per-step mean reversion in [0, 1].  All neutral at 0;
+               the wind is not observed (the obs stays the gym's 15 floats).
+               Any non-zero value enables the "wind" field ((N,6) f32: mean
+               wind xyz, gust xyz).
     """
 
     def __init__(self, num_envs: int, variant: str = "gym",
@@ -150,10 +187,13 @@ class DroneBatch:
                  env_id_offset: int = 0, max_steps: int | None = None,
                  keep_terminal_obs: bool = False, monitor: bool = False,
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
-                 tag_radius: float | None = None, crash_penalty: float | None = None):
+                 tag_radius: float | None = None, crash_penalty: float | None = None,
+                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
+                 gust_rate: float = 0.0):
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
         check_smoothing(variant, motor_alpha, rate_penalty)
+        wind = check_wind(variant, drag, wind_speed, gust_sigma, gust_rate, max_steps)
         tag_radius, crash_penalty = check_tag(variant, tag_radius, crash_penalty, num_envs,
                                               env_id_offset)
         if dtype not in (torch.float64, torch.float32):
@@ -202,6 +242,10 @@ class DroneBatch:
         self.tag_radius, self.crash_penalty = TAG_RADIUS, CRASH_PENALTY
         if variant == "tag":
             self.set_tag(tag_radius, crash_penalty)
+        self.drag = self.wind_speed = self.gust_sigma = self.gust_rate = 0.0
+        self.wind_enabled = False
+        if any(wind):
+            self.set_wind(*wind)
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -482,6 +526,22 @@ class DroneBatch:
         rr, cc = ctypes.c_float(), ctypes.c_float()
         check(self.L.dr_get_tag(self.handle, ctypes.byref(rr), ctypes.byref(cc)), self.handle)
         self.tag_radius, self.crash_penalty = float(rr.value), float(cc.value)
+
+    def set_wind(self, drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
+                 gust_rate: float = 0.0) -> None:
+        """variant="gym": linear drag, per-episode mean wind and gusts
+        (dr_set_wind) for every step / rollout enqueued
+        after the call; a new wind_speed applies from each env's next reset.
+        The first call with a non-zero value allocates the "wind" field and
+        draws every env's mean wind for its current episode: it waits for the
+        device and must not be made while a graph is being captured (a
+        captured graph keeps the kernels and values it was captured with)."""
+        if self.variant != "gym":
+            raise ValueError(f"set_wind needs variant='gym', not {self.variant!r}")
+        w = check_wind(self.variant, drag, wind_speed, gust_sigma, gust_rate, self.max_steps)
+        check(self.L.dr_set_wind(self.handle, *w), self.handle)
+        self.drag, self.wind_speed, self.gust_sigma, self.gust_rate = w
+        self.wind_enabled = self.wind_enabled or any(w)
 
     def set_reset_uniforms(self, u) -> None:
         """rng='host': (N,5) f64 uniforms ((N,14) for "moving") consumed by

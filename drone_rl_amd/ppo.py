@@ -100,13 +100,22 @@ class PPOConfig:
     # variant.  One shared policy flies both roles (the role is obs[18])
     tag_radius: float | None = None
     crash_penalty: float | None = None
+    # variant "gym" only: linear drag per unit mass
+    # (1/s), the bound of each axis of the per-episode mean wind (m/s), the
+    # gusts' stationary std per axis (m/s) and their per-step mean reversion
+    # in [0, 1].  All neutral at 0; the policy does not observe the wind
+    drag: float = 0.0
+    wind_speed: float = 0.0
+    gust_sigma: float = 0.0
+    gust_rate: float = 0.0
 
     def __post_init__(self):
-        from .env import OBS_DIM, check_smoothing, check_tag
+        from .env import OBS_DIM, check_smoothing, check_tag, check_wind
         if self.variant not in OBS_DIM:
             raise ValueError(f"unknown variant {self.variant!r}")
         check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
         check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
+        check_wind(self.variant, self.drag, self.wind_speed, self.gust_sigma, self.gust_rate)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -138,7 +147,9 @@ class PPOTrainer:
                               keep_terminal_obs=cfg.bootstrap_timeouts,
                               dtype=torch.float64 if cfg.state_dtype == "f64" else torch.float32,
                               motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty,
-                              tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty)
+                              tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty,
+                              drag=cfg.drag, wind_speed=cfg.wind_speed,
+                              gust_sigma=cfg.gust_sigma, gust_rate=cfg.gust_rate)
         if cfg.initial_eps:
             self.env.set("eps", torch.full((N,), float(cfg.initial_eps), dtype=torch.float64))
         od = self.env.obs_dim
@@ -326,7 +337,10 @@ class PPOTrainer:
         as on the eager path."""
         c = self.cfg
         if kind == "rollout":
+            e = self.env
+            # (the wind values also say which kernels the env launches)
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
+                    e.wind_enabled, e.drag, e.wind_speed, e.gust_sigma, e.gust_rate,
                     self.env.tag_radius, self.env.crash_penalty,
                     self.env.motor_alpha, self.env.rate_penalty)
         o = self.opt
@@ -593,8 +607,10 @@ class PPOTrainer:
         if self.cfg.variant == "rk4":
             # the attitude is a quaternion ("euler" would be derived from it)
             return tuple("quat" if k == "euler" else k for k in self._ENV_FIELDS)
+        # (a gym env carries its wind once enabled)
         return self._ENV_FIELDS + {"moving": ("motion",),
-                                   "smooth": ("motor",)}.get(self.cfg.variant, ())
+                                   "smooth": ("motor",)}.get(self.cfg.variant, ()) + \
+            (("wind",) if self.env.wind_enabled else ())
 
     def state_dict(self):
         """Everything needed to resume bit-for-bit on the same device count:
@@ -626,6 +642,11 @@ class PPOTrainer:
             self.opt.m.copy_(sd["adam"]["exp_avg"].to(self.device))
             self.opt.v.copy_(sd["adam"]["exp_avg_sq"].to(self.device))
             self.opt.t = int(sd["adam"]["step"])
+            if "wind" in sd["env"] and not self.env.wind_enabled:
+                # a wind checkpoint into a trainer built without wind: take
+                # the checkpoint's conditions
+                self.env.set_wind(*(sd["config"].get(k, 0.0) for k in
+                                    ("drag", "wind_speed", "gust_sigma", "gust_rate")))
             for k, v in sd["env"].items():
                 self.env.set(k, v)
             self.obs[0].copy_(sd["last_obs"].to(self.device))

@@ -74,6 +74,14 @@ def main(argv=None):
                     help="--variant smooth: lag blend dt / (tau + dt) in (0, 1] (1 = no lag)")
     ap.add_argument("--rate-penalty", type=float, default=0.0,
                     help="--variant smooth: penalty on |command - motor force|^2 per step")
+    ap.add_argument("--drag", type=float, default=0.0,
+                    help="--variant gym: linear drag per unit mass in 1/s (0 = vacuum)")
+    ap.add_argument("--wind-speed", type=float, default=0.0,
+                    help="--variant gym: bound of each axis of the per-episode mean wind, m/s")
+    ap.add_argument("--gust-sigma", type=float, default=0.0,
+                    help="--variant gym: stationary std of each gust axis, m/s")
+    ap.add_argument("--gust-rate", type=float, default=0.0,
+                    help="--variant gym: the gusts' per-step mean reversion in [0, 1]")
     ap.add_argument("--sb3-defaults", action="store_true",
                     help="SB3 PPO defaults of the reference (n_steps 2048, batch 64, 64x64)")
     ap.add_argument("--checkpoint", default="./dd_gpu.pt")
@@ -110,6 +118,8 @@ def main(argv=None):
                   bootstrap_timeouts=a.bootstrap_timeouts,
                   motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty,
                   tag_radius=a.tag_radius, crash_penalty=a.crash_penalty,
+                  drag=a.drag, wind_speed=a.wind_speed, gust_sigma=a.gust_sigma,
+                  gust_rate=a.gust_rate,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

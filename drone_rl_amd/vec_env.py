@@ -35,8 +35,9 @@ except Exception:  # noqa: BLE001 - SB3 absent (this image)
     _VecEnvBase = object
 
 # "motor": the smooth variant's motor forces; "quat": the rk4 variant's
-# attitude (DroneBatch raises on the others)
-_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat")
+# attitude (DroneBatch raises on the others); "wind": a gym batch's mean wind
+# and gust once wind is enabled
+_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat", "wind")
 _SCALAR = {"current_step": int, "ep_num": int, "eps": float}
 
 
@@ -50,7 +51,9 @@ class BatchedDroneVecEnv(_VecEnvBase):
                  dtype: torch.dtype = torch.float64, device=None, seed: int | None = None,
                  monitor: bool = True, rng: str = "philox", env_id_offset: int = 0,
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
-                 tag_radius: float | None = None, crash_penalty: float | None = None):
+                 tag_radius: float | None = None, crash_penalty: float | None = None,
+                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
+                 gust_rate: float = 0.0):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
@@ -58,7 +61,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
                                 env_id_offset=env_id_offset, keep_terminal_obs=True,
                                 monitor=True, motor_alpha=motor_alpha,
                                 rate_penalty=rate_penalty, tag_radius=tag_radius,
-                                crash_penalty=crash_penalty)
+                                crash_penalty=crash_penalty, drag=drag, wind_speed=wind_speed,
+                                gust_sigma=gust_sigma, gust_rate=gust_rate)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -129,6 +133,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
             raise AttributeError("only the 'smooth' variant has attribute 'motor'")
         if attr_name == "quat" and self.batch.variant != "rk4":
             raise AttributeError("only the 'rk4' variant has attribute 'quat'")
+        if attr_name == "wind" and not self.batch.wind_enabled:
+            raise AttributeError("attribute 'wind' needs a 'gym' batch with wind enabled")
         if attr_name in _STATE:
             v = self.batch.get_host(attr_name)
             return [v[i].copy() for i in idx]
@@ -203,12 +209,16 @@ class DroneVectorEnv:
     def __init__(self, num_envs: int, device=None, seed: int = 0,
                  dtype: torch.dtype = torch.float64, split_time_limit: bool = False,
                  as_tensors: bool = False, variant: str = "gym",
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0):
+                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
+                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
+                 gust_rate: float = 0.0):
         if variant not in ("gym", "smooth", "rk4"):
             raise ValueError("DroneVectorEnv wraps the 'gym', 'smooth' or 'rk4' variant")
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=True, keep_terminal_obs=True, monitor=True,
-                                motor_alpha=motor_alpha, rate_penalty=rate_penalty)
+                                motor_alpha=motor_alpha, rate_penalty=rate_penalty,
+                                drag=drag, wind_speed=wind_speed, gust_sigma=gust_sigma,
+                                gust_rate=gust_rate)
         self.num_envs = num_envs
         od = self.batch.obs_dim
         self.single_observation_space = make_box(-np.inf, np.inf, (od,), np.float32)

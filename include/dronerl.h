@@ -127,9 +127,12 @@ enum dr_field {   /* dr_get_state / dr_set_state, all device buffers      */
                                (DR_FIELD_TARGET is then the motion centre)  */
     DR_FIELD_MOTOR = 11,    /* (N,4) f32  smooth variant: the force each motor
                                applies (the lag filter's state)             */
-    DR_FIELD_QUAT = 12      /* (N,4) in the handle's state dtype (f64 or f32),
+    DR_FIELD_QUAT = 12,     /* (N,4) in the handle's state dtype (f64 or f32),
                                rk4 variant: the attitude (w, x, y, z); a zero
                                quaternion written here is the caller's error */
+    DR_FIELD_WIND = 13      /* (N,6) f32  gym variant after a non-neutral
+                               dr_set_wind: the episode's mean wind xyz, the
+                               gust xyz (m/s); DR_ERR_UNSUPPORTED before      */
 };
 
 typedef struct dr_config {
@@ -250,6 +253,47 @@ int dr_get_smoothing(const dr_handle *h, float *alpha, float *rate_penalty);
    reads them back (either pointer may be NULL). */
 int dr_set_tag(dr_handle *h, float tag_radius, float crash_penalty);
 int dr_get_tag(const dr_handle *h, float *tag_radius, float *crash_penalty);
+
+/* DR_VARIANT_GYM: wind, gusts and linear drag, an
+   option of the gym env, all four neutral at 0:
+     drag        k >= 0, linear drag per unit mass (1/s), k * dt <= 1
+     wind_speed  W >= 0, bound of each axis of the per-episode mean wind (m/s)
+     gust_sigma  s >= 0, stationary standard deviation of each gust axis (m/s)
+     gust_rate   beta in [0, 1], the gust's per-step mean reversion
+   Per env six f32 words are state (DR_FIELD_WIND): the mean wind m and the
+   gust g.  With (key, counter) -> Philox4x32-10 block, gid the global env id
+   and words -> uniforms u = w * 2^-32 as for the reset draws:
+     reset into episode ep:  m_k = W * f32(2 u_k - 1) from the block of counter
+       (ep, gid_lo, gid_hi, TAG_RESET | 2) (f32 product), g = 0; in
+       DR_RNG_HOST_UNIFORMS mode too (the host buffer keeps its (N,5) meaning)
+     step from step counter s of episode ep, ahead of the gym step:
+       xi_k = f32(2 u_k - 1) from the first three words of the block of counter
+       (ep, gid_lo, gid_hi, 0x47000000 | s);
+       g_k <- b * g_k + c * xi_k in f32, one rounding per operation, with
+       b = 1.0f - beta and c = (float)((double)s * sqrt(3 (1 - (double)b^2)))
+       formed here once per call (xi has variance 1/3: the stationary std of g
+       is s);
+       w_k = (S)(m_k + g_k) (f32 add, then the cast to the state scalar S);
+       v_k <- v_k + ((S)k * (w_k - v_k)) * dt;
+       then the gym step, unchanged, on the updated velocity.
+   The observation stays the gym's 15 floats: the wind is not observed.
+   The first non-neutral call allocates the six arrays and fills m for every
+   env's CURRENT episode (so m is a function of key, env and episode whenever
+   wind was switched on): that call is synchronous (it waits for the device)
+   and must not be made during graph capture.  Until then the handle allocates
+   nothing more and launches exactly the gym's kernels; afterwards it launches
+   the wind kernels, also at all-zero parameters (where every result equals
+   the gym's).  A later change of W applies from each env's next reset; k, s,
+   beta apply to work enqueued after the call.  dr_rollout* on such a handle
+   runs the one-role kernel at every size and is bitwise k dr_step calls.
+   DR_ERR_INVALID for a null handle, a negative or non-finite value, beta > 1
+   or k * dt > 1; DR_ERR_UNSUPPORTED on the other variants and on handles
+   with max_steps >= 2^24 (the gust counter holds s in 24 bits).  dr_get_wind
+   reads the four values back (any pointer may be NULL). */
+int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma,
+                float gust_rate);
+int dr_get_wind(const dr_handle *h, float *drag, float *wind_speed, float *gust_sigma,
+                float *gust_rate);
 
 /* Synthetic random policy: out (n,4) f32 i.i.d. U[lo,hi) from Philox keyed
    by seed with counter (env_id_offset + i, step).  Not part of the

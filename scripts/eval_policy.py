@@ -21,7 +21,15 @@ config: per role the mean return of the episodes that ended and the share of
 them in which that drone crashed, and per pair tag_fraction (the share of
 steps with the two closer than tag_radius) and the mean distance.
 
+A gym checkpoint is evaluated under wind, gusts and linear drag (DESIGN.md
+section 17) with --drag / --wind-speed / --gust-sigma / --gust-rate; a flag
+not given takes the value of the checkpoint's config (0 for checkpoints from
+before the option), so a wind-trained policy is by default evaluated under
+its training conditions and any gym policy can be put under any wind (the
+wind is not observed: the two kinds of policy are interchangeable).
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
+                                [--drag 0.5 --wind-speed 2 --gust-sigma 0.5 --gust-rate 0.1]
 """
 import argparse
 import json
@@ -34,12 +42,21 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM, check_tag  # noqa: E402
+from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM, check_tag, check_wind  # noqa: E402
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
+WIND_KEYS = ("drag", "wind_speed", "gust_sigma", "gust_rate")
+
+
+def wind_of(cfg, args):
+    """The four wind values: the command line's, else the checkpoint's."""
+    return tuple(float(cfg.get(k, 0.0)) if getattr(args, k) is None else getattr(args, k)
+                 for k in WIND_KEYS)
+
+
 @torch.no_grad()
-def evaluate(ckpt, eps, envs, steps, seed, deterministic):
+def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0)):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -52,7 +69,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic):
     pol = ActorCritic(OBS_DIM[variant], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
     pol.flat.data.copy_(sd["flat"].to(dev))
     env = DroneBatch(envs, variant, device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
-                     motor_alpha=alpha, rate_penalty=lam)
+                     motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND_KEYS, wind)))
     env.set("eps", torch.full((envs,), float(eps), dtype=torch.float64))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
@@ -149,6 +166,10 @@ def main():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--seed", type=int, default=123)
+    for k in WIND_KEYS:
+        ap.add_argument("--" + k.replace("_", "-"), type=float, default=None,
+                        help="gym checkpoints: evaluate under this wind parameter "
+                             "(default: the checkpoint's)")
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
     cfg = torch.load(a.ckpt, map_location="cpu", weights_only=True)["config"]
@@ -159,10 +180,14 @@ def main():
     if out["variant"] == "tag":
         out["tag_radius"], out["crash_penalty"] = check_tag("tag", cfg.get("tag_radius"),
                                                             cfg.get("crash_penalty"))
+    wind = wind_of(cfg, a)
+    if any(wind) or out["variant"] == "gym":
+        # raises for a non-gym checkpoint with a wind flag
+        out.update(zip(WIND_KEYS, check_wind(out["variant"], *wind)))
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (
             evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det) if out["variant"] == "tag"
-            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det))
+            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind))
     print(json.dumps(out), flush=True)
 
 
