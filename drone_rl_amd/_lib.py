@@ -37,7 +37,8 @@ DR_RNG_HOST_UNIFORMS = 1
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
-          "ep_length": 9, "motion": 10, "motor": 11, "quat": 12, "wind": 13}
+          "ep_length": 9, "motion": 10, "motor": 11, "quat": 12, "wind": 13,
+          "waypoint": 14}
 
 
 class dr_config(ctypes.Structure):
@@ -95,6 +96,8 @@ SIGNATURES = {
     "dr_get_tag": (c_int, [_P, _P, _P]),
     "dr_set_wind": (c_int, [_P, c_float, c_float, c_float, c_float]),
     "dr_get_wind": (c_int, [_P, _P, _P, _P, _P]),
+    "dr_set_waypoints": (c_int, [_P, c_float, c_float]),
+    "dr_get_waypoints": (c_int, [_P, _P, _P]),
     "dr_rollout": (c_int, [_P, c_int32, _P, _P, _P, _P, _P]),
     "dr_rollout_timed": (c_int, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "dr_rollout_random": (c_int, [_P, c_int32, c_uint64, c_int64, c_float, c_float, _P, _P,

@@ -15,7 +15,9 @@
 // fourth word is one more array of S) and advances the state by one RK4 step;
 // its obs has 16 floats.  A gym handle with wind
 // enabled (dr_set_wind) adds 6 f32 arrays, the mean wind and the gust, and no
-// obs float.
+// obs float.  A gym handle on waypoint courses
+// (dr_set_waypoints) adds 2 i32 arrays, the waypoint's index and the reach
+// counter, and moves its target on when it is reached.
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -407,12 +409,16 @@ __device__ inline void moving_reset_regs(const EnvView<S> &v, int64_t i, int mod
 // kernel-variant tag of this file, not a public dr_variant value.  A gym
 // handle's kernels are instantiated on it once its wind arrays exist.
 constexpr int KVAR_WIND = 64;
+// The gym variant with waypoint courses enabled (dr_set_waypoints; DESIGN.md
+// section 18): likewise a tag of this file.  Wind and waypoints exclude each
+// other on a handle.
+constexpr int KVAR_WAYPOINT = 65;
 
 // ---- smooth-control variant (DR_VARIANT_SMOOTH) ----
 // Observation width of a variant.
 template <int VAR>
 constexpr int od_of() {
-    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND)
+    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND || VAR == KVAR_WAYPOINT)
                ? 15
                : (VAR == DR_VARIANT_MOVING
                       ? 18
@@ -502,6 +508,39 @@ __device__ inline void wind_pre(S st[F_N], const float m[3], float g[3],
         const S w = (S)(m[k] + g[k]);
         st[F_VEL + k] = st[F_VEL + k] + ((S)va.k * (w - st[F_VEL + k])) * dt;
     }
+}
+
+// ---- waypoint courses (dr_set_waypoints) ----
+// Per env two i32 words, the index j of the current waypoint within the
+// episode and the count q of reaches since enabling, in two arrays at
+// EnvView::mot (the handle's second allocation, same stride).  The current
+// waypoint is the gym's stored target.
+template <>
+struct VarArgs<KVAR_WAYPOINT> {
+    float radius;  // reach radius R > 0
+    float bonus;   // reach bonus B >= 0
+};
+
+// Waypoint number `j` (>= 1) of env `gid` in episode `ep`, into st[F_TGT ..]:
+// the expressions of gym_reset_regs on a Philox block of its own.  While
+// eps == 0 the products are exact zeros, the waypoint is (0, 0, 1) and the draw
+// is skipped.  Called inside the divergent `reached` branch only: a reach is a
+// rare event, and the ten rounds stay off the step's straight-line path.
+template <typename S>
+__device__ inline void waypoint_draw(S st[F_N], uint32_t k0, uint32_t k1, uint64_t gid,
+                                     int32_t ep, double eps, int32_t j) {
+    double u[3] = {0.0, 0.0, 0.0};
+    if (eps != 0.0) {
+        const u32x4 r = philox4x32_10(u32x4{(uint32_t)ep, (uint32_t)gid, (uint32_t)(gid >> 32),
+                                            TAG_WAYPOINT | (uint32_t)j},
+                                      k0, k1);
+        u[0] = u01_w32(r.x);
+        u[1] = u01_w32(r.y);
+        u[2] = u01_w32(r.z);
+    }
+    st[F_TGT + 0] = (S)(eps * u[0]);
+    st[F_TGT + 1] = (S)(eps * u[1]);
+    st[F_TGT + 2] = (S)(eps * u[2] + 1.0 + 0.0);
 }
 
 // ---- tag variant (DR_VARIANT_TAG) ----
@@ -608,8 +647,12 @@ __device__ inline MotorMix motor_mix(float4 act) {
                     ((-a0 + a1) + a2) - a3, ((a0 - a1) + a2) - a3};
 }
 
+// wp / reached: the waypoint option's radius and bonus and its reach flag
+// (KVAR_WAYPOINT only).
 template <typename S, int VAR>
-__device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash) {
+__device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash,
+                                       const VarArgs<VAR> *wp = nullptr,
+                                       bool *reached = nullptr) {
     // thrust / torques (drone.py:106, 113-117): f32 sums, f64 factor product,
     // the yaw torque stays f32.
     const float thr = mx.thr;
@@ -673,7 +716,13 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
         const S dy = st[F_POS + 1] - st[F_TGT + 1];
         const S dz = st[F_POS + 2] - st[F_TGT + 2];
         const S d = m_sqrt((dx * dx + dy * dy) + dz * dz);
-        if constexpr (VAR != DR_VARIANT_VECTORIZED) {
+        if constexpr (VAR == KVAR_WAYPOINT) {
+            // the gym's form on the handle's radius and bonus; the caller
+            // advances the course where `reached`
+            r = (S)0.01 * -d;
+            *reached = d < (S)wp->radius;
+            if (*reached) r += (S)wp->bonus;
+        } else if constexpr (VAR != DR_VARIANT_VECTORIZED) {
             r = (S)0.01 * -d;
             if (d < (S)0.05) r += (S)1;
         } else {
@@ -692,8 +741,9 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
 }
 
 template <typename S, int VAR>
-__device__ inline S physics_step(S st[F_N], float4 act, S dt, bool &crash) {
-    return physics_step_mixed<S, VAR>(st, motor_mix(act), dt, crash);
+__device__ inline S physics_step(S st[F_N], float4 act, S dt, bool &crash,
+                                 const VarArgs<VAR> *wp = nullptr, bool *reached = nullptr) {
+    return physics_step_mixed<S, VAR>(st, motor_mix(act), dt, crash, wp, reached);
 }
 
 // ---- rk4 variant (DR_VARIANT_RK4) ----
@@ -894,8 +944,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     constexpr bool RK4 = VAR == DR_VARIANT_RK4;
     // (and the gym env with wind, the gym's step behind a disturbance)
     constexpr bool WIND = VAR == KVAR_WIND;
+    // (and the gym env on a waypoint course: the gym's step, a target that
+    // moves on when it is reached)
+    constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
     constexpr bool GYMSTATE =
-        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND;
+        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND || WAYPT;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
@@ -964,6 +1017,13 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             wg[k] = *at(v.mot + (3 + k) * v.stride, i);
         }
     }
+    // waypoints: the index within the episode and the reach counter
+    int32_t wj = 0, wq = 0;
+    int32_t *const p_wp = reinterpret_cast<int32_t *>(v.mot);
+    if constexpr (WAYPT) {
+        wj = *at(p_wp, i);
+        wq = *at(p_wp + v.stride, i);
+    }
     if constexpr (TAG) {
         // nothing in the step reads the stored target: a reset writes it
 #pragma unroll
@@ -1016,12 +1076,15 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         wind_pre<S>(st, wm, wg, va, v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old,
                     step, v.dt);
     bool crash;
+    bool reached = false;
     S r;
     if constexpr (SMOOTH) {
         // the physics sees the lagged forces, not the command
         r = physics_step<S, VAR>(st, smooth_filter(act, fm, va.alpha, dev_sq), v.dt, crash);
     } else if constexpr (RK4) {
         r = rk4_step<S>(st, qd, motor_mix(act), v.dt, rk4_h6<S>(va), crash);
+    } else if constexpr (WAYPT) {
+        r = physics_step<S, VAR>(st, act, v.dt, crash, &va, &reached);
     } else {
         r = physics_step<S, VAR>(st, act, v.dt, crash);
     }
@@ -1064,9 +1127,22 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
     for (int k = 0; k < (TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
     if constexpr (RK4) asm volatile("" ::"v"(qd));
+    if constexpr (WAYPT) asm volatile("" ::"v"(wj), "v"(wq));
     if (live) {
         st_out(at(io.rew, i), rf);
         st_out(at(io.done, i), (uint8_t)done);
+    }
+    if constexpr (WAYPT) {
+        // the course moves on, ahead of the terminal obs and of a reset
+        // (which overwrites the target it stores)
+        if (reached && live) {
+            wj += 1;
+            wq += 1;
+            waypoint_draw<S>(st, v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old,
+                             eps_old, wj);
+#pragma unroll
+            for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
+        }
     }
 
     float ret = 0.f;
@@ -1098,6 +1174,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
                     for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                 }
+                if constexpr (WAYPT) wj = 0;   // a new course; q counts on
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
                 if constexpr (SMOOTH) {
@@ -1155,6 +1232,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                 st_out(at(v.mot + k * v.stride, i), wm[k]);
                 st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
             }
+        }
+        if constexpr (WAYPT) {
+            st_out(at(p_wp, i), wj);
+            st_out(at(p_wp + v.stride, i), wq);
         }
     }
     DR_STAMP(4);
@@ -1222,8 +1303,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     constexpr bool TAG = VAR == DR_VARIANT_TAG;
     constexpr bool RK4 = VAR == DR_VARIANT_RK4;
     constexpr bool WIND = VAR == KVAR_WIND;
+    // (and the gym env on a waypoint course: the gym's step, a target that
+    // moves on when it is reached)
+    constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
     constexpr bool GYMSTATE =
-        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND;
+        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND || WAYPT;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
@@ -1266,6 +1350,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             wm[k] = *at(v.mot + k * v.stride, i);
             wg[k] = *at(v.mot + (3 + k) * v.stride, i);
         }
+    }
+    // waypoints: the index and the reach counter, carried in registers over
+    // the launch, as is the current waypoint (the target)
+    int32_t wj = 0, wq = 0;
+    int32_t *const p_wp = reinterpret_cast<int32_t *>(v.mot);
+    if constexpr (WAYPT) {
+        wj = *at(p_wp, i);
+        wq = *at(p_wp + v.stride, i);
     }
     if constexpr (GYMSTATE) {
 #pragma unroll
@@ -1336,8 +1428,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         if constexpr (WIND)
             wind_pre<S>(st, wm, wg, va, vk.seed_lo, vk.seed_hi, gid, ep_num, step, v.dt);
         bool crash;
+        bool reached = false;
         S r;
         if constexpr (RK4) r = rk4_step<S>(st, qd, mx, v.dt, rk4_h6<S>(va), crash);
+        else if constexpr (WAYPT)
+            r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, &va, &reached);
         else r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
         bool done;
@@ -1369,6 +1464,16 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             }
             st_out(at(io.done + row, i), (uint8_t)done);
         }
+        if constexpr (WAYPT) {
+            // the course moves on (env_step_kernel), all in registers; the
+            // target is written back at the end, as after a reset
+            if (reached && live) {
+                wj += 1;
+                wq += 1;
+                waypoint_draw<S>(st, vk.seed_lo, vk.seed_hi, gid, ep_num, eps, wj);
+                reset_any = true;
+            }
+        }
         if constexpr (GYMLIKE) {
             if (done && io.auto_reset) {
                 step = 0;
@@ -1386,6 +1491,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
                         for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                     }
+                    if constexpr (WAYPT) wj = 0;
                 } else {
                     moving_reset_regs(vk, i, 0, st, cen, mp, ep_num, eps, nd_ok ? nd : nullptr);
                     nd_ok = false;
@@ -1461,6 +1567,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(wm[k]), "v"(wg[k]));
         }
+        if constexpr (WAYPT) asm volatile("" ::"v"(wj), "v"(wq));
         // Two steps ahead, in two registers that alternate (the loop is
         // unrolled by two so each keeps its role): step t's action was
         // loaded at the top of step t-2; younger than that load are step
@@ -1510,6 +1617,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
             }
         }
+        if constexpr (WAYPT) {
+            st_out(at(p_wp, i), wj);
+            st_out(at(p_wp + v.stride, i), wq);
+        }
+        // (waypoints: or reached a waypoint, which moves the target too)
         if (reset_any) {
             if constexpr (GYMSTATE) {
 #pragma unroll
@@ -2426,6 +2538,32 @@ __global__ void wind_field_kernel(float *wind, int64_t stride, int64_t n, const 
     }
 }
 
+// Waypoints: a new course (j = 0) for every env (mask null: dr_reset) or those
+// with mask[i] != 0 (dr_reset_masked); the reach counter q stays.  Runs behind
+// the gym's env_reset_kernel on the same stream, as wind_fill_kernel does.
+__global__ __launch_bounds__(kBlock) void waypoint_restart_kernel(int32_t *wp, int64_t n,
+                                                                  const uint8_t *mask) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (mask && !mask[i]) return;
+    wp[i] = 0;
+}
+
+// DR_FIELD_WAYPOINT, as wind_field_kernel: row j of the (k,2) i32 buffer `io`
+// (index within the episode, reaches since enabling).
+__global__ void waypoint_field_kernel(int32_t *wp, int64_t stride, int64_t n, const int32_t *ids,
+                                      int64_t k, int32_t *io, int set) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const int64_t i = ids ? (int64_t)ids[j] : j;
+    if (i < 0 || i >= n) return;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (set) wp[c * stride + i] = io[j * 2 + c];
+        else io[j * 2 + c] = wp[c * stride + i];
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void random_actions_kernel(
     int64_t n, uint32_t k0, uint32_t k1, int64_t env_off, uint64_t step,
     float lo, float span, float4 *out) {
@@ -2465,6 +2603,12 @@ struct dr_handle {
     float drag = 0.0f, wind_speed = 0.0f, gust_sigma = 0.0f, gust_rate = 0.0f;
     float gust_b = 1.0f, gust_c = 0.0f;
     float *wind = nullptr;
+    // DR_VARIANT_GYM (dr_set_waypoints): the reach radius and bonus, passed to
+    // each launch, and the two i32 arrays of `stride` elements (j, q) the
+    // first call allocates; while null the handle launches the gym's kernels.
+    // At most one of `wind` and `wp` is set.
+    float reach_radius = 0.0f, reach_bonus = 0.0f;
+    int32_t *wp = nullptr;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -2502,7 +2646,9 @@ EnvView<S> view_of(const dr_handle *h) {
     v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH ||
              h->cfg.variant == DR_VARIANT_RK4)
                 ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
-                : (h->cfg.variant == DR_VARIANT_GYM ? h->wind : nullptr);
+                : (h->cfg.variant == DR_VARIANT_GYM
+                       ? (h->wp ? reinterpret_cast<float *>(h->wp) : h->wind)
+                       : nullptr);
     v.n = h->n;
     v.env_id_offset = h->cfg.env_id_offset;
     v.host_u = h->host_u;
@@ -2548,6 +2694,8 @@ int with_state(const dr_handle *h, F &&f) {
             case DR_VARIANT_GYM:
                 // with wind enabled: the gym-with-wind kernels
                 if (h->wind) return f(s, std::integral_constant<int, KVAR_WIND>{});
+                // on a waypoint course: the gym-with-waypoints kernels
+                if (h->wp) return f(s, std::integral_constant<int, KVAR_WAYPOINT>{});
                 return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
             case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
             case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
@@ -2570,6 +2718,7 @@ VarArgs<VAR> var_args(const dr_handle *h) {
         return VarArgs<VAR>{h->cfg.dt / 6.0, (float)h->cfg.dt / 6.0f};
     else if constexpr (VAR == KVAR_WIND)
         return VarArgs<VAR>{h->drag, h->gust_b, h->gust_c, h->wind_speed};
+    else if constexpr (VAR == KVAR_WAYPOINT) return VarArgs<VAR>{h->reach_radius, h->reach_bonus};
     else return VarArgs<VAR>{};
 }
 
@@ -2599,16 +2748,30 @@ int launch_wind_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
     return DR_OK;
 }
 
+// A new course (j = 0) for every env (mask: the masked envs), enqueued on `st`.
+int launch_waypoint_restart(dr_handle *h, const uint8_t *mask, hipStream_t st) {
+    hipLaunchKernelGGL(waypoint_restart_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->wp,
+                       h->n, mask);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string("waypoint_restart_kernel: ") + hipGetErrorString(e));
+    return DR_OK;
+}
+
 int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
                    int init, hipStream_t st) {
     return with_state(h, [&](auto s, auto var) {
         // a wind handle resets as the gym does (the wind is not observed),
-        // then draws the new episodes' mean wind behind it
+        // then draws the new episodes' mean wind behind it; a waypoint
+        // handle likewise, then starts the new episodes' courses
         constexpr int V = decltype(var)::value;
-        constexpr int RV = V == KVAR_WIND ? (int)DR_VARIANT_GYM : V;
+        constexpr int RV = (V == KVAR_WIND || V == KVAR_WAYPOINT) ? (int)DR_VARIANT_GYM : V;
         int rc = launch_reset<typename decltype(s)::type, RV>(h, mask, obs, mode, init, st);
         if constexpr (V == KVAR_WIND) {
             if (rc == DR_OK) rc = launch_wind_fill(h, mask, st);
+        }
+        if constexpr (V == KVAR_WAYPOINT) {
+            if (rc == DR_OK) rc = launch_waypoint_restart(h, mask, st);
         }
         return rc;
     });
@@ -2683,9 +2846,11 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
     // The smooth, tag and rk4 variants have the one-role kernel only (the lag
     // state, the partner exchange and the quaternion step are not built into
     // the warp-specialised forms), whatever the override says.
-    // (likewise a gym handle with wind: m and g ride in its registers)
+    // (likewise a gym handle with wind: m and g ride in its registers; and one
+    // on a waypoint course: j and q do)
     constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG ||
-                              VAR == DR_VARIANT_RK4 || VAR == KVAR_WIND;
+                              VAR == DR_VARIANT_RK4 || VAR == KVAR_WIND ||
+                              VAR == KVAR_WAYPOINT;
     const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
@@ -2789,6 +2954,22 @@ int wind_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, flo
     DeviceGuard g(h->cfg.device);
     hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
                        h->wind, h->stride, h->n, ids, k, io, set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return DR_OK;
+}
+
+// DR_FIELD_WAYPOINT of dr_get_state / dr_gather_state / dr_set_state.
+int waypoint_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, int32_t *io,
+                   int set, void *stream) {
+    if (!h->wp)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    std::string(who) + ": waypoint exists only after dr_set_waypoints");
+    if (k == 0) return DR_OK;
+    DeviceGuard g(h->cfg.device);
+    hipLaunchKernelGGL(waypoint_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0,
+                       as_stream(stream), h->wp, h->stride, h->n, ids, k, io, set);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -2925,6 +3106,7 @@ int dr_destroy(dr_handle *h) {
         (void)hipDeviceSynchronize();
         (void)hipFree(h->mem);
         if (h->wind) (void)hipFree(h->wind);
+        if (h->wp) (void)hipFree(h->wp);
     }
     delete h;
     return DR_OK;
@@ -3070,6 +3252,9 @@ int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (field == DR_FIELD_QUAT) return quat_field(h, "dr_get_state", nullptr, h->n, out, 0, stream);
     if (field == DR_FIELD_WIND)
         return wind_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
+    if (field == DR_FIELD_WAYPOINT)
+        return waypoint_field(h, "dr_get_state", nullptr, h->n, static_cast<int32_t *>(out), 0,
+                              stream);
     if (int rc = euler_refused(h, "dr_get_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
@@ -3096,6 +3281,9 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
     if (field == DR_FIELD_QUAT) return quat_field(h, "dr_gather_state", env_ids, k, out, 0, stream);
     if (field == DR_FIELD_WIND)
         return wind_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
+    if (field == DR_FIELD_WAYPOINT)
+        return waypoint_field(h, "dr_gather_state", env_ids, k, static_cast<int32_t *>(out), 0,
+                              stream);
     if (int rc = euler_refused(h, "dr_gather_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_gather_state: unknown field");
@@ -3125,6 +3313,9 @@ int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     if (field == DR_FIELD_WIND)
         return wind_field(h, "dr_set_state", nullptr, h->n,
                           const_cast<float *>(static_cast<const float *>(in)), 1, stream);
+    if (field == DR_FIELD_WAYPOINT)
+        return waypoint_field(h, "dr_set_state", nullptr, h->n,
+                              const_cast<int32_t *>(static_cast<const int32_t *>(in)), 1, stream);
     if (int rc = euler_refused(h, "dr_set_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
@@ -3222,6 +3413,9 @@ int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma, fl
         return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: max_steps must be below 2^24");
     const bool neutral =
         drag == 0.0f && wind_speed == 0.0f && gust_sigma == 0.0f && gust_rate == 0.0f;
+    // a handle has wind or a waypoint course, not both
+    if (h->wp && !neutral)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: the handle is on a waypoint course");
     const bool enable = !h->wind && !neutral;
     float *w = nullptr;
     DeviceGuard g(h->cfg.device);
@@ -3267,6 +3461,56 @@ int dr_get_wind(const dr_handle *h, float *drag, float *wind_speed, float *gust_
     if (wind_speed) *wind_speed = h->wind_speed;
     if (gust_sigma) *gust_sigma = h->gust_sigma;
     if (gust_rate) *gust_rate = h->gust_rate;
+    return DR_OK;
+}
+
+int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_waypoints: null handle");
+    // written so that NaN fails every test
+    constexpr float kMax = 3.4028234663852886e38f;
+    if (!(reach_radius > 0.0f && reach_radius <= kMax))
+        return fail(h, DR_ERR_INVALID, "dr_set_waypoints: reach_radius must be finite and > 0");
+    if (!(reach_bonus >= 0.0f && reach_bonus <= kMax))
+        return fail(h, DR_ERR_INVALID, "dr_set_waypoints: reach_bonus must be finite and >= 0");
+    if (h->cfg.variant != DR_VARIANT_GYM)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    "dr_set_waypoints: only DR_VARIANT_GYM has waypoint courses");
+    if (h->wind)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: the handle has wind enabled");
+    // the waypoint counter carries the index, below the step limit, in its
+    // low 24 bits
+    if (h->cfg.max_steps >= (1 << 24))
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: max_steps must be below 2^24");
+    if (!h->wp) {
+        // j = q = 0 for every env; the state may be in use on any stream:
+        // drain, allocate and clear, drain
+        DeviceGuard g(h->cfg.device);
+        int32_t *w = nullptr;
+        const size_t bytes = (size_t)2 * h->stride * sizeof(int32_t);
+        hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        e = hipMalloc(reinterpret_cast<void **>(&w), bytes);
+        if (e != hipSuccess)
+            return fail(h, DR_ERR_NOMEM,
+                        std::string("dr_set_waypoints: hipMalloc: ") + hipGetErrorString(e));
+        e = hipMemset(w, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(w);
+            return fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        }
+        h->wp = w;
+    }
+    h->reach_radius = reach_radius;
+    h->reach_bonus = reach_bonus;
+    return DR_OK;
+}
+
+int dr_get_waypoints(const dr_handle *h, float *reach_radius, float *reach_bonus) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_waypoints: null handle");
+    if (h->cfg.variant != DR_VARIANT_GYM) return DR_ERR_UNSUPPORTED;
+    if (reach_radius) *reach_radius = h->reach_radius;
+    if (reach_bonus) *reach_bonus = h->reach_bonus;
     return DR_OK;
 }
 

@@ -41,6 +41,11 @@ CRASH_PENALTY = 0.0
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
 # (N, width) f32 fields a single variant owns
 _F32_ROW_FIELDS = {"motion": 9, "motor": 4, "wind": 6}
+# (N, width) i32 fields
+_I32_ROW_FIELDS = {"waypoint": 2}
+# dr_set_waypoints' defaults where only one of the two values is given
+REACH_RADIUS = 0.25
+REACH_BONUS = 1.0
 
 
 def quat_to_euler(q) -> np.ndarray:
@@ -117,6 +122,33 @@ def check_wind(variant: str, drag=0.0, wind_speed=0.0, gust_sigma=0.0, gust_rate
     return tuple(vals)
 
 
+def check_waypoints(variant: str, reach_radius=None, reach_bonus=None,
+                    max_steps: int | None = None, wind=None) -> tuple[float, float] | None:
+    """The argument rules of dr_set_waypoints, raised
+    as ValueError before any device work.  None / None means the option is off
+    and returns None; giving one of the two enables it with the other at its
+    default (0.25 / 1.0).  reach_radius must be finite and > 0 in f32,
+    reach_bonus finite and >= 0; the variant must be "gym", its step limit
+    below 2^24, and `wind` (the four dr_set_wind values, if given) all zero.
+    Returns the two values as the kernels see them (rounded to f32)."""
+    if reach_radius is None and reach_bonus is None:
+        return None
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = float(np.float32(REACH_RADIUS if reach_radius is None else reach_radius))
+        b = float(np.float32(REACH_BONUS if reach_bonus is None else reach_bonus))
+    if not (0.0 < r < float("inf")):
+        raise ValueError(f"reach_radius must be finite and > 0, got {reach_radius!r}")
+    if not (0.0 <= b < float("inf")):
+        raise ValueError(f"reach_bonus must be finite and >= 0, got {reach_bonus!r}")
+    if variant != "gym":
+        raise ValueError(f"reach_radius / reach_bonus need variant='gym', not {variant!r}")
+    if max_steps is not None and int(max_steps) >= 1 << 24:
+        raise ValueError("waypoint courses need max_steps below 2^24")
+    if wind is not None and any(float(w) != 0.0 for w in wind):
+        raise ValueError("a gym env has wind or a waypoint course, not both")
+    return r, b
+
+
 def check_tag(variant: str, tag_radius, crash_penalty, num_envs: int | None = None,
               env_id_offset: int = 0) -> tuple[float, float]:
     """The argument rules of the "tag" variant (dr_create / dr_set_tag), raised
@@ -179,6 +211,14 @@ class DroneBatch:
                the wind is not observed (the obs stays the gym's 15 floats).
                Any non-zero value enables the "wind" field ((N,6) f32: mean
                wind xyz, gust xyz).
+    reach_radius, reach_bonus
+               "gym" only: a waypoint course.  The
+               target moves on to a fresh draw when the drone comes closer
+               than reach_radius (> 0), and that step's reward gains
+               reach_bonus (>= 0).  None / None = off; giving one enables the
+               option with the other at its default (0.25 / 1.0), and with it
+               the "waypoint" field ((N,2) i32: index within the episode,
+               reaches since enabling).  Not together with wind.
     """
 
     def __init__(self, num_envs: int, variant: str = "gym",
@@ -189,11 +229,13 @@ class DroneBatch:
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
                  tag_radius: float | None = None, crash_penalty: float | None = None,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0):
+                 gust_rate: float = 0.0,
+                 reach_radius: float | None = None, reach_bonus: float | None = None):
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
         check_smoothing(variant, motor_alpha, rate_penalty)
         wind = check_wind(variant, drag, wind_speed, gust_sigma, gust_rate, max_steps)
+        course = check_waypoints(variant, reach_radius, reach_bonus, max_steps, wind)
         tag_radius, crash_penalty = check_tag(variant, tag_radius, crash_penalty, num_envs,
                                               env_id_offset)
         if dtype not in (torch.float64, torch.float32):
@@ -244,8 +286,12 @@ class DroneBatch:
             self.set_tag(tag_radius, crash_penalty)
         self.drag = self.wind_speed = self.gust_sigma = self.gust_rate = 0.0
         self.wind_enabled = False
+        self.reach_radius = self.reach_bonus = 0.0
+        self.waypoints_enabled = False
         if any(wind):
             self.set_wind(*wind)
+        if course is not None:
+            self.set_waypoints(*course)
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -413,6 +459,8 @@ class DroneBatch:
             return torch.empty(n, dtype=torch.float32, **where)
         if field in _F32_ROW_FIELDS:
             return torch.empty(n, _F32_ROW_FIELDS[field], dtype=torch.float32, **where)
+        if field in _I32_ROW_FIELDS:
+            return torch.empty(n, _I32_ROW_FIELDS[field], dtype=torch.int32, **where)
         if field == "quat":
             return torch.empty(n, 4, dtype=self.dtype, **where)
         return torch.empty(n, dtype=torch.int32, **where)
@@ -469,6 +517,9 @@ class DroneBatch:
             elif field in _F32_ROW_FIELDS:
                 out = torch.empty(k, _F32_ROW_FIELDS[field], dtype=torch.float32,
                                   device=self.device)
+            elif field in _I32_ROW_FIELDS:
+                out = torch.empty(k, _I32_ROW_FIELDS[field], dtype=torch.int32,
+                                  device=self.device)
             else:
                 out = torch.empty(k, dtype=torch.int32, device=self.device)
         ids = env_ids.to(device=self.device, dtype=torch.int32).contiguous()
@@ -491,6 +542,8 @@ class DroneBatch:
             dt, shape = torch.float32, (self.num_envs,)
         elif field in _F32_ROW_FIELDS:
             dt, shape = torch.float32, (self.num_envs, _F32_ROW_FIELDS[field])
+        elif field in _I32_ROW_FIELDS:
+            dt, shape = torch.int32, (self.num_envs, _I32_ROW_FIELDS[field])
         else:
             dt, shape = torch.int32, (self.num_envs,)
         v = torch.as_tensor(value, dtype=dt).to(self.device).reshape(shape).contiguous()
@@ -539,9 +592,30 @@ class DroneBatch:
         if self.variant != "gym":
             raise ValueError(f"set_wind needs variant='gym', not {self.variant!r}")
         w = check_wind(self.variant, drag, wind_speed, gust_sigma, gust_rate, self.max_steps)
+        if self.waypoints_enabled and any(w):
+            raise ValueError("a gym env has wind or a waypoint course, not both")
         check(self.L.dr_set_wind(self.handle, *w), self.handle)
         self.drag, self.wind_speed, self.gust_sigma, self.gust_rate = w
         self.wind_enabled = self.wind_enabled or any(w)
+
+    def set_waypoints(self, reach_radius: float | None = None,
+                      reach_bonus: float | None = None) -> None:
+        """variant="gym": fly a waypoint course (dr_set_waypoints, DESIGN.md
+        section 18) with this reach radius and bonus (None = 0.25 / 1.0) in
+        every step / rollout enqueued after the call.  The first call
+        allocates the "waypoint" field, zeroed: it waits for the device and
+        must not be made while a graph is being captured (a captured graph
+        keeps the kernels and values it was captured with).  The option
+        cannot be switched off again."""
+        if self.variant != "gym":
+            raise ValueError(f"set_waypoints needs variant='gym', not {self.variant!r}")
+        if reach_radius is None and reach_bonus is None:
+            reach_radius = REACH_RADIUS
+        rb = check_waypoints(self.variant, reach_radius, reach_bonus, self.max_steps,
+                             (1.0,) if self.wind_enabled else None)
+        check(self.L.dr_set_waypoints(self.handle, *rb), self.handle)
+        self.reach_radius, self.reach_bonus = rb
+        self.waypoints_enabled = True
 
     def set_reset_uniforms(self, u) -> None:
         """rng='host': (N,5) f64 uniforms ((N,14) for "moving") consumed by

@@ -108,14 +108,22 @@ class PPOConfig:
     wind_speed: float = 0.0
     gust_sigma: float = 0.0
     gust_rate: float = 0.0
+    # variant "gym" only: a waypoint course.  The target
+    # moves on when the drone comes closer than reach_radius, and that step's
+    # reward gains reach_bonus.  None / None = off; giving one enables the
+    # option with the other at its default (0.25 / 1.0).  Not together with wind
+    reach_radius: float | None = None
+    reach_bonus: float | None = None
 
     def __post_init__(self):
-        from .env import OBS_DIM, check_smoothing, check_tag, check_wind
+        from .env import OBS_DIM, check_smoothing, check_tag, check_waypoints, check_wind
         if self.variant not in OBS_DIM:
             raise ValueError(f"unknown variant {self.variant!r}")
         check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
         check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
-        check_wind(self.variant, self.drag, self.wind_speed, self.gust_sigma, self.gust_rate)
+        wind = check_wind(self.variant, self.drag, self.wind_speed, self.gust_sigma,
+                          self.gust_rate)
+        check_waypoints(self.variant, self.reach_radius, self.reach_bonus, wind=wind)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -149,7 +157,10 @@ class PPOTrainer:
                               motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty,
                               tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty,
                               drag=cfg.drag, wind_speed=cfg.wind_speed,
-                              gust_sigma=cfg.gust_sigma, gust_rate=cfg.gust_rate)
+                              gust_sigma=cfg.gust_sigma, gust_rate=cfg.gust_rate,
+                              reach_radius=cfg.reach_radius, reach_bonus=cfg.reach_bonus)
+        # waypoint courses: the reaches of the last rollout (device scalar)
+        self._wp_gain = None
         if cfg.initial_eps:
             self.env.set("eps", torch.full((N,), float(cfg.initial_eps), dtype=torch.float64))
         od = self.env.obs_dim
@@ -262,6 +273,8 @@ class PPOTrainer:
         fwd = self.infer if self.use_fused else self.policy
         # noise counter of step t = num_updates * T + t, its base on the device
         self._ctr.fill_(self.num_updates * T)
+        # waypoint courses: the reach counters before and after the rollout
+        wq0 = self.env.get("waypoint")[:, 1].sum() if self.env.waypoints_enabled else None
         key = self._graph_key("rollout")
         if self._rgraph is not None and key != self._rkey:
             self._rgraph = None       # a host scalar baked into the graph changed
@@ -288,6 +301,8 @@ class PPOTrainer:
             self._rgraph = g
         if self.trajectory is not None:
             self.trajectory.flush()
+        if wq0 is not None:
+            self._wp_gain = self.env.get("waypoint")[:, 1].sum() - wq0
         _, last_values = fwd(self.obs[T])
         K.gae(self.rewards, self.values, self.dones[:T], last_values, self.dones[T],
               cfg.gamma, cfg.gae_lambda, advantages=self.adv, returns=self.ret)
@@ -341,6 +356,7 @@ class PPOTrainer:
             # (the wind values also say which kernels the env launches)
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
                     e.wind_enabled, e.drag, e.wind_speed, e.gust_sigma, e.gust_rate,
+                    e.waypoints_enabled, e.reach_radius, e.reach_bonus,
                     self.env.tag_radius, self.env.crash_penalty,
                     self.env.motor_alpha, self.env.rate_penalty)
         o = self.opt
@@ -565,7 +581,9 @@ class PPOTrainer:
         """Mean return / length of the episodes that ended in the last rollout
         (VecMonitor's ep_info_buffer role; all-reduced over ranks).  Variant
         "tag" adds the mean return per role: the reward is zero-sum, so the
-        mean over both roles says nothing."""
+        mean over both roles says nothing.  On a waypoint course
+        ep_waypoints_mean is the rollout's reaches (the increase of the
+        counters q) over the episodes that ended in it."""
         done = self.dones[1:].bool()
         terms = [torch.where(done, self.ep_ret, 0).sum(),
                  torch.where(done, self.ep_len, 0).sum().float(),
@@ -576,6 +594,9 @@ class PPOTrainer:
             for role in (0, 1):
                 d = done[:, role::2]
                 terms += [torch.where(d, self.ep_ret[:, role::2], 0).sum(), d.sum().float()]
+        wp = self.env.waypoints_enabled and self._wp_gain is not None
+        if wp:
+            terms.append(self._wp_gain.float())
         s = torch.stack(terms)
         D.allreduce_sum_(s, self.world, group=self.pg)
         n = max(s[2].item(), 1.0)
@@ -584,6 +605,8 @@ class PPOTrainer:
         if tag:
             out["ep_rew_mean_pursuer"] = s[3].item() / max(s[4].item(), 1.0)
             out["ep_rew_mean_evader"] = s[5].item() / max(s[6].item(), 1.0)
+        if wp:
+            out["ep_waypoints_mean"] = s[-1].item() / n
         return out
 
     def learn(self, total_timesteps: int, log_every: int = 1, logger=print):
@@ -610,7 +633,8 @@ class PPOTrainer:
         # (a gym env carries its wind once enabled)
         return self._ENV_FIELDS + {"moving": ("motion",),
                                    "smooth": ("motor",)}.get(self.cfg.variant, ()) + \
-            (("wind",) if self.env.wind_enabled else ())
+            (("wind",) if self.env.wind_enabled else ()) + \
+            (("waypoint",) if self.env.waypoints_enabled else ())
 
     def state_dict(self):
         """Everything needed to resume bit-for-bit on the same device count:
@@ -647,6 +671,10 @@ class PPOTrainer:
                 # the checkpoint's conditions
                 self.env.set_wind(*(sd["config"].get(k, 0.0) for k in
                                     ("drag", "wind_speed", "gust_sigma", "gust_rate")))
+            if "waypoint" in sd["env"] and not self.env.waypoints_enabled:
+                # likewise a waypoint checkpoint: the checkpoint's course
+                self.env.set_waypoints(sd["config"].get("reach_radius"),
+                                       sd["config"].get("reach_bonus"))
             for k, v in sd["env"].items():
                 self.env.set(k, v)
             self.obs[0].copy_(sd["last_obs"].to(self.device))

@@ -82,6 +82,12 @@ def main(argv=None):
                     help="--variant gym: stationary std of each gust axis, m/s")
     ap.add_argument("--gust-rate", type=float, default=0.0,
                     help="--variant gym: the gusts' per-step mean reversion in [0, 1]")
+    ap.add_argument("--reach-radius", type=float, default=None,
+                    help="--variant gym: fly waypoint courses; the target moves on inside "
+                         "this distance (default 0.25 when only --reach-bonus is given)")
+    ap.add_argument("--reach-bonus", type=float, default=None,
+                    help="--variant gym: reward added in the step of a reach (default 1.0 "
+                         "when only --reach-radius is given)")
     ap.add_argument("--sb3-defaults", action="store_true",
                     help="SB3 PPO defaults of the reference (n_steps 2048, batch 64, 64x64)")
     ap.add_argument("--checkpoint", default="./dd_gpu.pt")
@@ -120,6 +126,7 @@ def main(argv=None):
                   tag_radius=a.tag_radius, crash_penalty=a.crash_penalty,
                   drag=a.drag, wind_speed=a.wind_speed, gust_sigma=a.gust_sigma,
                   gust_rate=a.gust_rate,
+                  reach_radius=a.reach_radius, reach_bonus=a.reach_bonus,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

@@ -36,8 +36,9 @@ except Exception:  # noqa: BLE001 - SB3 absent (this image)
 
 # "motor": the smooth variant's motor forces; "quat": the rk4 variant's
 # attitude (DroneBatch raises on the others); "wind": a gym batch's mean wind
-# and gust once wind is enabled
-_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat", "wind")
+# and gust once wind is enabled; "waypoint": a gym batch's (index, reaches)
+# on a waypoint course
+_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat", "wind", "waypoint")
 _SCALAR = {"current_step": int, "ep_num": int, "eps": float}
 
 
@@ -53,7 +54,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
                  tag_radius: float | None = None, crash_penalty: float | None = None,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0):
+                 gust_rate: float = 0.0,
+                 reach_radius: float | None = None, reach_bonus: float | None = None):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
@@ -62,7 +64,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
                                 monitor=True, motor_alpha=motor_alpha,
                                 rate_penalty=rate_penalty, tag_radius=tag_radius,
                                 crash_penalty=crash_penalty, drag=drag, wind_speed=wind_speed,
-                                gust_sigma=gust_sigma, gust_rate=gust_rate)
+                                gust_sigma=gust_sigma, gust_rate=gust_rate,
+                                reach_radius=reach_radius, reach_bonus=reach_bonus)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -135,6 +138,8 @@ class BatchedDroneVecEnv(_VecEnvBase):
             raise AttributeError("only the 'rk4' variant has attribute 'quat'")
         if attr_name == "wind" and not self.batch.wind_enabled:
             raise AttributeError("attribute 'wind' needs a 'gym' batch with wind enabled")
+        if attr_name == "waypoint" and not self.batch.waypoints_enabled:
+            raise AttributeError("attribute 'waypoint' needs a 'gym' batch on a waypoint course")
         if attr_name in _STATE:
             v = self.batch.get_host(attr_name)
             return [v[i].copy() for i in idx]
@@ -211,14 +216,16 @@ class DroneVectorEnv:
                  as_tensors: bool = False, variant: str = "gym",
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0):
+                 gust_rate: float = 0.0,
+                 reach_radius: float | None = None, reach_bonus: float | None = None):
         if variant not in ("gym", "smooth", "rk4"):
             raise ValueError("DroneVectorEnv wraps the 'gym', 'smooth' or 'rk4' variant")
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=True, keep_terminal_obs=True, monitor=True,
                                 motor_alpha=motor_alpha, rate_penalty=rate_penalty,
                                 drag=drag, wind_speed=wind_speed, gust_sigma=gust_sigma,
-                                gust_rate=gust_rate)
+                                gust_rate=gust_rate, reach_radius=reach_radius,
+                                reach_bonus=reach_bonus)
         self.num_envs = num_envs
         od = self.batch.obs_dim
         self.single_observation_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -256,6 +263,16 @@ class DroneVectorEnv:
                                 "l": self._out(torch.where(d, self.batch.ep_len, 0))}
             infos["_episode"] = self._out(d)
         return self._out(obs), self._out(rew), self._out(term), self._out(trunc), infos
+
+    def get_attr(self, name: str):
+        """A state field of every env as one (N, ...) array; "waypoint" (the
+        index within the episode, the reaches since enabling) on a waypoint
+        course."""
+        if name == "waypoint" and not self.batch.waypoints_enabled:
+            raise AttributeError("attribute 'waypoint' needs a batch on a waypoint course")
+        if name not in _STATE and name not in _SCALAR:
+            raise AttributeError(f"DroneVectorEnv has no attribute {name!r}")
+        return self.batch.get_host(name)
 
     def close(self):
         self.batch.close()

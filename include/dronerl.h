@@ -130,9 +130,13 @@ enum dr_field {   /* dr_get_state / dr_set_state, all device buffers      */
     DR_FIELD_QUAT = 12,     /* (N,4) in the handle's state dtype (f64 or f32),
                                rk4 variant: the attitude (w, x, y, z); a zero
                                quaternion written here is the caller's error */
-    DR_FIELD_WIND = 13      /* (N,6) f32  gym variant after a non-neutral
+    DR_FIELD_WIND = 13,     /* (N,6) f32  gym variant after a non-neutral
                                dr_set_wind: the episode's mean wind xyz, the
                                gust xyz (m/s); DR_ERR_UNSUPPORTED before      */
+    DR_FIELD_WAYPOINT = 14  /* (N,2) i32  gym variant after dr_set_waypoints:
+                               j, the current waypoint's index within the
+                               episode, and q, the reaches since enabling;
+                               DR_ERR_UNSUPPORTED before                      */
 };
 
 typedef struct dr_config {
@@ -294,6 +298,52 @@ int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma,
                 float gust_rate);
 int dr_get_wind(const dr_handle *h, float *drag, float *wind_speed, float *gust_sigma,
                 float *gust_rate);
+
+/* DR_VARIANT_GYM: waypoint courses, an option of the
+   gym env: the target moves on when the drone reaches it.
+     reach_radius  R > 0, finite: the distance below which a waypoint counts
+     reach_bonus   B >= 0, finite: the reward added in the step of a reach
+   Per env two i32 words are state (DR_FIELD_WAYPOINT): j, the index of the
+   current waypoint within the episode (= the reaches this episode; every reset
+   sets it to 0), and q, the reaches since enabling (resets never touch it).
+   The current waypoint is DR_FIELD_TARGET.  One step of an env with global id
+   gid in episode ep (ep_num), curriculum eps and target c, S the state scalar:
+     1. the gym physics, unchanged; d = sqrt((dx dx + dy dy) + dz dz) of the
+        new position minus c, in S, the gym's expression;
+     2. r = (S)0.01 * (-d); reached = d < (S)R (false for NaN); where reached,
+        r += (S)B;
+     3. crash, the step counter and done are the gym's;
+     4. where reached: j <- j + 1, q <- q + 1, and with u_k = w_k * 2^-32 of the
+        first three words of the Philox4x32-10 block of counter
+        (ep, gid_lo, gid_hi, 0x57000000 | j) under the handle's seed,
+        c <- ((S)(eps u_0), (S)(eps u_1), (S)(eps u_2 + 1.0 + 0.0)), f64
+        operations and a cast, the expressions of the reset's target draw
+        (while eps == 0, c = (0, 0, 1) and no block is drawn); at most one
+        advance per step;
+     5. the obs, and the terminal obs, are the gym's 15 floats of the state
+        AFTER the advance: the next waypoint is observed only once it is current;
+     6. done with auto-reset: the gym reset, and j <- 0; q keeps its value, a
+        reach in the terminal step included.  Without auto-reset the advanced
+        state stays.
+   At eps = 0 with (R, B) = (0.05, 1) every output equals the gym's; at any
+   values obs[:, :12], done, ep_num and the resets do (the physics never reads
+   the target).  In DR_RNG_HOST_UNIFORMS mode waypoints come from Philox too
+   (the host buffer keeps its (N,5) meaning).
+   The first call allocates the two arrays, zeroed: that call is synchronous
+   (it waits for the device) and must not be made during graph capture.  Until
+   then the handle allocates nothing more and launches exactly the gym's
+   kernels; afterwards it launches the waypoint kernels, and there is no way
+   back.  Later calls change R and B only, for work enqueued after the call
+   (launch arguments).  dr_rollout* on such a handle runs the one-role kernel
+   at every size and is bitwise k dr_step calls.
+   DR_ERR_INVALID for a null handle, R <= 0, B < 0 or a non-finite value;
+   DR_ERR_UNSUPPORTED on the other variants, on a handle whose wind is enabled
+   and on handles with max_steps >= 2^24 (the counter holds j in 24 bits).  On
+   a waypoint handle a non-neutral dr_set_wind is DR_ERR_UNSUPPORTED.
+   dr_get_waypoints reads the two values back, (0, 0) before enabling (either
+   pointer may be NULL). */
+int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus);
+int dr_get_waypoints(const dr_handle *h, float *reach_radius, float *reach_bonus);
 
 /* Synthetic random policy: out (n,4) f32 i.i.d. U[lo,hi) from Philox keyed
    by seed with counter (env_id_offset + i, step).  Not part of the

@@ -28,8 +28,18 @@ before the option), so a wind-trained policy is by default evaluated under
 its training conditions and any gym policy can be put under any wind (the
 wind is not observed: the two kinds of policy are interchangeable).
 
+A gym checkpoint is flown on waypoint courses with
+--reach-radius / --reach-bonus; a flag not given takes the checkpoint's value
+(off for checkpoints trained without the option; giving one enables it with
+the other at its default).  The obs is the gym's 15 floats, so any gym policy
+flies a course and a course policy flies the plain gym env
+(--reach-radius 0 switches a course checkpoint's option off).  On a course the
+result adds waypoints_per_episode, the reach counters' sum over the episodes
+that ended.
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
                                 [--drag 0.5 --wind-speed 2 --gust-sigma 0.5 --gust-rate 0.1]
+                                [--reach-radius 0.25 --reach-bonus 1]
 """
 import argparse
 import json
@@ -42,7 +52,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import HOVER, MOTOR_MAX, OBS_DIM, check_tag, check_wind  # noqa: E402
+from drone_rl_amd.env import (HOVER, MOTOR_MAX, OBS_DIM, check_tag, check_waypoints,  # noqa: E402
+                              check_wind)
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
@@ -55,8 +66,19 @@ def wind_of(cfg, args):
                  for k in WIND_KEYS)
 
 
+def course_of(cfg, args):
+    """(reach_radius, reach_bonus) or (None, None): the command line's values,
+    else the checkpoint's; --reach-radius 0 switches the option off."""
+    r = cfg.get("reach_radius") if args.reach_radius is None else args.reach_radius
+    b = cfg.get("reach_bonus") if args.reach_bonus is None else args.reach_bonus
+    if args.reach_radius is not None and args.reach_radius == 0:
+        return None, None
+    return r, b
+
+
 @torch.no_grad()
-def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0)):
+def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0),
+             course=(None, None)):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -69,7 +91,8 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     pol = ActorCritic(OBS_DIM[variant], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
     pol.flat.data.copy_(sd["flat"].to(dev))
     env = DroneBatch(envs, variant, device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
-                     motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND_KEYS, wind)))
+                     motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND_KEYS, wind)),
+                     reach_radius=course[0], reach_bonus=course[1])
     env.set("eps", torch.full((envs,), float(eps), dtype=torch.float64))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
@@ -101,12 +124,19 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
         ret_sum += float(ep_ret[db].sum())
         len_sum += float(ep_len[db].float().sum())
         n_crash += float((db & (ep_len < 200)).sum())
+    reaches = float(env.get("waypoint")[:, 1].sum()) if env.waypoints_enabled else None
     env.close()
     n = max(n_done, 1.0)
-    return {"deterministic": deterministic, "episodes": int(n_done),
-            "ep_rew_mean": ret_sum / n, "ep_len_mean": len_sum / n,
-            "crash_frac": n_crash / n, "bonus_step_frac": in_bonus / steps,
-            "cmd_dev_sq_mean": dev_sq / steps}
+    out = {"deterministic": deterministic, "episodes": int(n_done),
+           "ep_rew_mean": ret_sum / n, "ep_len_mean": len_sum / n,
+           "crash_frac": n_crash / n, "bonus_step_frac": in_bonus / steps,
+           "cmd_dev_sq_mean": dev_sq / steps}
+    if reaches is not None:
+        # on a course bonus_step_frac is the share of steps with a reach
+        # (given a bonus above 0.01 R); per episode: all reaches counted since
+        # enabling over the episodes that ended
+        out["waypoints_per_episode"] = reaches / n
+    return out
 
 
 @torch.no_grad()
@@ -170,6 +200,11 @@ def main():
         ap.add_argument("--" + k.replace("_", "-"), type=float, default=None,
                         help="gym checkpoints: evaluate under this wind parameter "
                              "(default: the checkpoint's)")
+    ap.add_argument("--reach-radius", type=float, default=None,
+                    help="gym checkpoints: fly waypoint courses with this reach radius "
+                         "(default: the checkpoint's; 0 = the plain gym env)")
+    ap.add_argument("--reach-bonus", type=float, default=None,
+                    help="gym checkpoints: the reward added in the step of a reach")
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
     cfg = torch.load(a.ckpt, map_location="cpu", weights_only=True)["config"]
@@ -184,10 +219,15 @@ def main():
     if any(wind) or out["variant"] == "gym":
         # raises for a non-gym checkpoint with a wind flag
         out.update(zip(WIND_KEYS, check_wind(out["variant"], *wind)))
+    course = course_of(cfg, a)
+    # raises for a non-gym checkpoint with a course flag, or wind and a course
+    rb = check_waypoints(out["variant"], *course, wind=wind)
+    if rb is not None:
+        out["reach_radius"], out["reach_bonus"] = rb
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (
             evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det) if out["variant"] == "tag"
-            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind))
+            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind, course))
     print(json.dumps(out), flush=True)
 
 

@@ -1,0 +1,205 @@
+"""The gym env's waypoint courses (dr_set_waypoints)
+without a GPU: the ids and tables, the argument rules of the C ABI, DroneBatch
+and PPOConfig (all before any device work), the NumPy restatement
+tests/waypoint_ref.py against the oracle's gym step at eps 0 with the gym's
+radius and bonus, and the waypoint draw as a function of (seed, env, episode,
+index, eps)."""
+import os
+
+import numpy as np
+import pytest
+
+import waypoint_ref
+from oracle import cref
+
+
+def _state(g):
+    s = {k: np.array(g[k], np.float64, order="C")
+         for k in ("pos", "vel", "euler", "omega", "target")}
+    s["step"] = np.array(g["step"], np.int32)
+    return s
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
+
+
+# ---- ids, tables, argument rules (no device work) ---------------------------
+def test_ids_tables_and_header():
+    from drone_rl_amd import _lib
+    assert _lib.FIELDS["waypoint"] == 14 and _lib.ABI_VERSION == 16
+    assert "dr_set_waypoints" in _lib.SIGNATURES and "dr_get_waypoints" in _lib.SIGNATURES
+    root = os.path.join(os.path.dirname(__file__), "..")
+    hdr = open(os.path.join(root, "include", "dronerl.h")).read()
+    assert "int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus);" in hdr
+    assert "int dr_get_waypoints(const dr_handle *h, float *reach_radius" in hdr
+    assert "DR_FIELD_WAYPOINT = 14" in hdr
+    assert "#define DR_ABI_VERSION 16" in hdr
+    common = open(os.path.join(root, "drone_rl_amd", "csrc", "common.h")).read()
+    assert "TAG_WAYPOINT = 0x57000000u" in common and waypoint_ref.TAG_WAYPOINT == 0x57000000
+
+
+def test_null_handle_is_refused_before_any_device_call():
+    import ctypes
+
+    from drone_rl_amd import _lib
+    L = _lib.lib()
+    assert L.dr_set_waypoints(None, 0.25, 1.0) == _lib.DR_ERR_INVALID
+    assert "dr_set_waypoints: null handle" in _lib.last_error()
+    x = ctypes.c_float()
+    assert L.dr_get_waypoints(None, ctypes.byref(x), None) == _lib.DR_ERR_INVALID
+    buf = (ctypes.c_int32 * 2)()
+    assert L.dr_get_state(None, _lib.FIELDS["waypoint"], buf, None) == _lib.DR_ERR_INVALID
+
+
+BAD = [dict(reach_radius=0.0), dict(reach_radius=-0.25), dict(reach_radius=float("nan")),
+       dict(reach_radius=float("inf")), dict(reach_radius=1e39), dict(reach_radius=1e-50),
+       dict(reach_bonus=-1.0), dict(reach_bonus=float("nan")), dict(reach_bonus=float("inf")),
+       dict(reach_bonus=1e39)]
+
+
+@pytest.mark.parametrize("bad", BAD, ids=lambda d: "-".join(f"{k}={v}" for k, v in d.items()))
+def test_bad_values_raise_without_a_device(bad):
+    from drone_rl_amd import DroneBatch
+    from drone_rl_amd.env import check_waypoints
+    from drone_rl_amd.ppo import PPOConfig
+    with pytest.raises(ValueError):
+        check_waypoints("gym", **bad)
+    with pytest.raises(ValueError):
+        DroneBatch(4, "gym", **bad)
+    with pytest.raises(ValueError):
+        PPOConfig(**bad)
+
+
+def test_variant_and_default_rules_need_no_device():
+    from drone_rl_amd import DroneBatch
+    from drone_rl_amd.env import check_waypoints
+    from drone_rl_amd.ppo import PPOConfig
+    assert check_waypoints("gym") is None                       # None / None: off
+    assert check_waypoints("gym", 0.5) == (0.5, 1.0)            # one given: the other's default
+    assert check_waypoints("gym", None, 2.5) == (0.25, 2.5)
+    assert check_waypoints("gym", 0.05, 0.0) == (float(np.float32(0.05)), 0.0)
+    cfg = PPOConfig(reach_radius=0.25, reach_bonus=1.0)
+    assert (cfg.reach_radius, cfg.reach_bonus) == (0.25, 1.0)
+    assert PPOConfig().reach_radius is None and PPOConfig().reach_bonus is None
+    for variant in ("vectorized", "moving", "smooth", "tag", "rk4"):
+        assert check_waypoints(variant) is None                 # off is fine anywhere
+        for kw in (dict(reach_radius=0.25), dict(reach_bonus=1.0)):
+            with pytest.raises(ValueError, match="variant='gym'"):
+                check_waypoints(variant, **kw)
+            with pytest.raises(ValueError):
+                DroneBatch(4, variant, **kw)
+            with pytest.raises(ValueError):
+                PPOConfig(variant=variant, num_envs=4, **kw)
+    with pytest.raises(ValueError, match="2\\^24"):
+        check_waypoints("gym", 0.25, max_steps=1 << 24)
+    with pytest.raises(ValueError, match="2\\^24"):
+        DroneBatch(4, "gym", reach_radius=0.25, max_steps=1 << 24)
+    check_waypoints("gym", 0.25, max_steps=(1 << 24) - 1)
+    # wind and waypoints exclude each other
+    with pytest.raises(ValueError, match="not both"):
+        check_waypoints("gym", 0.25, wind=(0.5, 0.0, 0.0, 0.0))
+    check_waypoints("gym", 0.25, wind=(0.0, 0.0, 0.0, 0.0))
+    with pytest.raises(ValueError, match="not both"):
+        DroneBatch(4, "gym", reach_radius=0.25, drag=0.5)
+    with pytest.raises(ValueError, match="not both"):
+        PPOConfig(reach_bonus=1.0, gust_sigma=0.5, gust_rate=0.1)
+
+
+# ---- the restatement --------------------------------------------------------
+def test_restatement_at_eps0_gym_radius_is_the_gym_step_bitwise(golden):
+    """On the reference's golden step vectors, with every target at the eps-0
+    waypoint (0, 0, 1) and some drones put inside the 5 cm radius: obs, reward,
+    done and every state word equal cref.gym_step's as bits; where the drone
+    reached, the counters moved and the waypoint is (0, 0, 1) again."""
+    g = golden("gym_step.npz")
+    n = len(g["action"])
+    a, b = _state(g), _state(g)
+    for s in (a, b):
+        s["target"][:] = [0.0, 0.0, 1.0]
+        # every third drone at rest 1 cm from the waypoint: it reaches
+        s["pos"][::3] = [0.006, -0.006, 1.005]
+        s["vel"][::3] = 0.0
+        s["euler"][::3] = 0.0
+        s["omega"][::3] = 0.0
+    b["ep_num"] = np.arange(n, dtype=np.int32) % 4001 + 1
+    b["eps"] = np.zeros(n)
+    b["waypoint"] = np.stack([np.arange(n) % 5, np.arange(n) * 3], 1).astype(np.int32)
+    wp0 = b["waypoint"].copy()
+    gids = np.arange(n, dtype=np.uint64) + (1 << 33)
+    og, rg, dg = cref.gym_step(a, g["action"])
+    ow, rw, dw, reached, d = waypoint_ref.waypoint_step(
+        b, g["action"], dict(reach_radius=0.05, reach_bonus=1.0), 5, gids)
+    np.testing.assert_array_equal(_bits(ow), _bits(og))
+    np.testing.assert_array_equal(_bits(rw), _bits(rg))
+    np.testing.assert_array_equal(dw, dg)
+    for k in ("pos", "vel", "euler", "omega", "target", "step"):
+        np.testing.assert_array_equal(_bits(b[k]), _bits(a[k]), err_msg=k)
+    assert reached.sum() >= n // 4 and (~reached).sum() >= n // 4
+    np.testing.assert_array_equal(reached, rg > 0)
+    np.testing.assert_array_equal(b["waypoint"], wp0 + reached[:, None])
+    assert not np.signbit(b["target"]).any()
+
+
+def test_reward_reach_and_advance_by_hand():
+    """One env at rest 0.1 m below its waypoint under hover thrust, eps 0.5,
+    R = 0.25, B = 2.5: r = -0.01 d + 2.5, j and q move on, the new waypoint is
+    the draw for (ep, j = 1) and the obs shows it; a second env 0.3 m away
+    reaches nothing and keeps everything."""
+    hover = np.full((2, 4), 9.81 / 4, np.float32)
+    s = {"pos": np.array([[0.0, 0.0, 0.9], [0.0, 0.0, 0.7]]), "vel": np.zeros((2, 3)),
+         "euler": np.zeros((2, 3)), "omega": np.zeros((2, 3)),
+         "target": np.array([[0.0, 0.0, 1.0], [0.0, 0.0, 1.0]]),
+         "step": np.zeros(2, np.int32), "ep_num": np.array([7, 7], np.int32),
+         "eps": np.array([0.5, 0.5]), "waypoint": np.array([[0, 10], [2, 20]], np.int32)}
+    obs, rew, done, reached, d = waypoint_ref.waypoint_step(
+        s, hover, dict(reach_radius=0.25, reach_bonus=2.5), 3, [40, 41])
+    assert reached.tolist() == [True, False] and not done.any()
+    assert abs(d[0] - 0.1) < 1e-6 and abs(d[1] - 0.3) < 1e-6
+    assert rew[0] == 0.01 * -d[0] + 2.5 and rew[1] == 0.01 * -d[1]
+    np.testing.assert_array_equal(s["waypoint"], [[1, 11], [2, 20]])
+    r = cref.philox([7, 40, 0, 0x57000001], [3, 0])
+    u = r[:3].astype(np.float64) / 2.0 ** 32
+    want = np.array([0.5 * u[0], 0.5 * u[1], 0.5 * u[2] + 1.0])
+    np.testing.assert_array_equal(s["target"][0], want)
+    np.testing.assert_array_equal(s["target"][1], [0.0, 0.0, 1.0])
+    np.testing.assert_array_equal(obs[0, 12:], (want - s["pos"][0]).astype(np.float32))
+    np.testing.assert_array_equal(obs[1, 12:], (s["target"][1] - s["pos"][1]).astype(np.float32))
+    # NaN compares false: no reach, no bonus
+    s["pos"][0, 0] = np.nan
+    _, rew, _, reached, _ = waypoint_ref.waypoint_step(
+        s, hover, dict(reach_radius=0.25, reach_bonus=2.5), 3, [40, 41])
+    assert not reached[0] and np.isnan(rew[0])
+
+
+def test_waypoint_is_a_function_of_key_env_episode_index_and_eps():
+    gids = np.arange(4096, dtype=np.uint64) + (1 << 40)
+    w = waypoint_ref.waypoint(11, gids, 3, 1, 1.3)
+    assert w.dtype == np.float64 and w.shape == (4096, 3)
+    # inside the eps box [0, eps)^2 x [1, 1 + eps), and filling it
+    assert w[:, :2].min() >= 0.0 and w[:, :2].max() < 1.3 and w[:, :2].max() > 1.29
+    assert w[:, 2].min() >= 1.0 and w[:, 2].max() < 2.3 and w[:, 2].min() < 1.01
+    assert abs(float(w[:, :2].mean()) - 0.65) < 0.02
+    np.testing.assert_array_equal(w[100:200], waypoint_ref.waypoint(11, gids[100:200], 3, 1, 1.3))
+    for other in (waypoint_ref.waypoint(12, gids, 3, 1, 1.3),        # seed
+                  waypoint_ref.waypoint(11, gids + np.uint64(1), 3, 1, 1.3),   # env
+                  waypoint_ref.waypoint(11, gids, 4, 1, 1.3),        # episode
+                  waypoint_ref.waypoint(11, gids, 3, 2, 1.3)):       # index
+        assert (other != w).all(axis=1).mean() > 0.99
+    # eps scales the same uniforms; at eps 0 the waypoint is exactly (0, 0, 1)
+    h = waypoint_ref.waypoint(11, gids, 3, 1, 0.65)
+    np.testing.assert_allclose(h[:, :2], w[:, :2] / 2, rtol=1e-15)
+    z = waypoint_ref.waypoint(11, gids, 3, 1, 0.0)
+    np.testing.assert_array_equal(z, np.broadcast_to([0.0, 0.0, 1.0], z.shape))
+    assert not np.signbit(z).any()
+    # per-env eps, and an index past 16 bits
+    e = np.where(np.arange(4096) % 2 == 0, 0.0, 1.3)
+    m = waypoint_ref.waypoint(11, gids, 3, 70001, e)
+    np.testing.assert_array_equal(m[::2], z[::2])
+    assert (m[1::2] != w[1::2]).all(axis=1).mean() > 0.99
+    # one Philox call by hand for one env
+    r = cref.philox([3, int(gids[5]) & 0xffffffff, int(gids[5]) >> 32, 0x57000000 | 70001],
+                    [11, 0])
+    u = r[:3].astype(np.float64) / 2.0 ** 32
+    np.testing.assert_array_equal(m[5], [1.3 * u[0], 1.3 * u[1], 1.3 * u[2] + 1.0 + 0.0])
