@@ -38,7 +38,7 @@ DR_RNG_HOST_UNIFORMS = 1
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
           "ep_length": 9, "motion": 10, "motor": 11, "quat": 12, "wind": 13,
-          "waypoint": 14}
+          "waypoint": 14, "airframe": 15}
 
 
 class dr_config(ctypes.Structure):
@@ -98,6 +98,8 @@ SIGNATURES = {
     "dr_get_wind": (c_int, [_P, _P, _P, _P, _P]),
     "dr_set_waypoints": (c_int, [_P, c_float, c_float]),
     "dr_get_waypoints": (c_int, [_P, _P, _P]),
+    "dr_set_airframe": (c_int, [_P, c_float, c_float, c_float]),
+    "dr_get_airframe": (c_int, [_P, _P, _P, _P]),
     "dr_rollout": (c_int, [_P, c_int32, _P, _P, _P, _P, _P]),
     "dr_rollout_timed": (c_int, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "dr_rollout_random": (c_int, [_P, c_int32, c_uint64, c_int64, c_float, c_float, _P, _P,

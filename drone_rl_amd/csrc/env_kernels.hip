@@ -18,6 +18,9 @@
 // obs float.  A gym handle on waypoint courses
 // (dr_set_waypoints) adds 2 i32 arrays, the waypoint's index and the reach
 // counter, and moves its target on when it is reached.
+// A gym handle with airframe randomisation (dr_set_airframe) adds 6 f32
+// arrays, the episode's mass scale, inertia scale and motor gains, and no obs
+// float.
 //
 // Physics: the reference's op order, restated from
 //   DroneEnv.step            /root/reference/drone.py:81-159
@@ -413,12 +416,17 @@ constexpr int KVAR_WIND = 64;
 // section 18): likewise a tag of this file.  Wind and waypoints exclude each
 // other on a handle.
 constexpr int KVAR_WAYPOINT = 65;
+// The gym variant with per-episode airframe randomisation enabled
+// (dr_set_airframe): likewise a tag of this file.  The
+// three options exclude each other pairwise on a handle.
+constexpr int KVAR_AIRFRAME = 66;
 
 // ---- smooth-control variant (DR_VARIANT_SMOOTH) ----
 // Observation width of a variant.
 template <int VAR>
 constexpr int od_of() {
-    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND || VAR == KVAR_WAYPOINT)
+    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND || VAR == KVAR_WAYPOINT ||
+            VAR == KVAR_AIRFRAME)
                ? 15
                : (VAR == DR_VARIANT_MOVING
                       ? 18
@@ -543,6 +551,56 @@ __device__ inline void waypoint_draw(S st[F_N], uint32_t k0, uint32_t k1, uint64
     st[F_TGT + 2] = (S)(eps * u[2] + 1.0 + 0.0);
 }
 
+// ---- airframe randomisation (dr_set_airframe) ----
+// Per env six f32 words, the episode's mass scale m, inertia scale s and
+// motor gains g0..g3, in six arrays at EnvView::mot (the handle's second
+// allocation, same stride).  Resets are their only writers.
+template <>
+struct VarArgs<KVAR_AIRFRAME> {
+    float sm;   // spread of the mass scale; the three are read by resets only
+    float si;   // spread of the inertia scale
+    float sg;   // spread of each motor gain
+};
+
+// The airframe of env `gid` in episode `ep`: af = (m, s, g0..g3), each
+// 1.0f + spread * xi in f32 (a product, a sum).  At spread 0 the value is
+// exactly 1.0f for every xi, so a block whose spreads are 0 is skipped.
+__device__ inline void airframe_draw(uint32_t k0, uint32_t k1, uint64_t gid, int32_t ep,
+                                     const VarArgs<KVAR_AIRFRAME> &va, float af[6]) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) af[k] = 1.0f;
+    if (va.sm != 0.f || va.si != 0.f) {
+        const u32x4 r = philox4x32_10(
+            u32x4{(uint32_t)ep, (uint32_t)gid, (uint32_t)(gid >> 32), TAG_AIRFRAME | 0u}, k0, k1);
+        af[0] = 1.0f + va.sm * wind_pm1(r.x);
+        af[1] = 1.0f + va.si * wind_pm1(r.y);
+    }
+    if (va.sg != 0.f) {
+        const u32x4 r = philox4x32_10(
+            u32x4{(uint32_t)ep, (uint32_t)gid, (uint32_t)(gid >> 32), TAG_AIRFRAME | 1u}, k0, k1);
+        af[2] = 1.0f + va.sg * wind_pm1(r.x);
+        af[3] = 1.0f + va.sg * wind_pm1(r.y);
+        af[4] = 1.0f + va.sg * wind_pm1(r.z);
+        af[5] = 1.0f + va.sg * wind_pm1(r.w);
+    }
+}
+
+// An env's airframe in registers: the six words and the reciprocals of the
+// two scales, IEEE f32 divides formed when the words are loaded or drawn, not
+// per step.
+struct Airframe {
+    float w[6];   // m, s, g0..g3
+    float im, is;
+    __device__ void recip() {
+        im = 1.0f / w[0];
+        is = 1.0f / w[1];
+    }
+};
+// a'_j = g_j a_j, the command the motor mixes are taken on
+__device__ inline float4 airframe_gain(const Airframe &a, float4 act) {
+    return make_float4(a.w[2] * act.x, a.w[3] * act.y, a.w[4] * act.z, a.w[5] * act.w);
+}
+
 // ---- tag variant (DR_VARIANT_TAG) ----
 // Envs 2j (pursuer) and 2j+1 (evader) sit in lanes l and l^1 of one wave.
 // The partner's value of a register: a lane <-> lane^1 swap that touches no
@@ -648,17 +706,26 @@ __device__ inline MotorMix motor_mix(float4 act) {
 }
 
 // wp / reached: the waypoint option's radius and bonus and its reach flag
-// (KVAR_WAYPOINT only).
+// (KVAR_WAYPOINT only).  af: the env's airframe (KVAR_AIRFRAME only: no other
+// instantiation forms or reads one).
 template <typename S, int VAR>
 __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash,
                                        const VarArgs<VAR> *wp = nullptr,
-                                       bool *reached = nullptr) {
+                                       bool *reached = nullptr,
+                                       const Airframe *af = nullptr) {
+    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
     // thrust / torques (drone.py:106, 113-117): f32 sums, f64 factor product,
     // the yaw torque stays f32.
     const float thr = mx.thr;
-    const S tau_phi = (S)kFactor * (S)mx.phi;
-    const S tau_theta = (S)kFactor * (S)mx.theta;
+    S tau_phi = (S)kFactor * (S)mx.phi;
+    S tau_theta = (S)kFactor * (S)mx.theta;
     const float tau_psi = kKyaw32 * mx.psi;
+    if constexpr (AIRF) {
+        // inertia s (Ixx, Iyy, Izz): one common scale leaves the gyroscopic
+        // terms as they are, so only the torques scale (the yaw torque below)
+        tau_phi = tau_phi * (S)af->is;
+        tau_theta = tau_theta * (S)af->is;
+    }
 
     // One sincos per angle: a shared range reduction yields exactly the
     // separate sin() and cos() results at half the instructions.
@@ -671,9 +738,17 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     const S r12 = sps * sth * cph - cps * sph;
     const S r22 = cth * cph;
     const S T = (S)thr;
-    const S acc0 = (S)0 + (r02 * T) / (S)kMass;      // (124)
-    const S acc1 = (S)0 + (r12 * T) / (S)kMass;
-    const S acc2 = (S)(-kG) + (r22 * T) / (S)kMass;
+    S acc0, acc1, acc2;
+    if constexpr (AIRF) {
+        // mass m kMass: the reciprocal's product where the gym divides
+        acc0 = (S)0 + (r02 * T) * (S)af->im;
+        acc1 = (S)0 + (r12 * T) * (S)af->im;
+        acc2 = (S)(-kG) + (r22 * T) * (S)af->im;
+    } else {
+        acc0 = (S)0 + (r02 * T) / (S)kMass;      // (124)
+        acc1 = (S)0 + (r12 * T) / (S)kMass;
+        acc2 = (S)(-kG) + (r22 * T) / (S)kMass;
+    }
     st[F_VEL + 0] += acc0 * dt;                      // (127)
     st[F_VEL + 1] += acc1 * dt;
     st[F_VEL + 2] += acc2 * dt;
@@ -702,7 +777,10 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     // Angular dynamics, diagonal inertia, old omega (135-139).
     const S wd0 = div_rcp(tau_phi - (S)(kIyy - kIzz) * w1 * w2, (S)kIxx, (S)(1.0 / kIxx));
     const S wd1 = div_rcp(tau_theta - (S)(kIzz - kIxx) * w0 * w2, (S)kIyy, (S)(1.0 / kIyy));
-    const S wd2 = div_rcp((S)tau_psi - (S)(kIxx - kIyy) * w0 * w1, (S)kIzz, (S)(1.0 / kIzz));
+    S tau_psi_s;
+    if constexpr (AIRF) tau_psi_s = (S)tau_psi * (S)af->is;
+    else tau_psi_s = (S)tau_psi;
+    const S wd2 = div_rcp(tau_psi_s - (S)(kIxx - kIyy) * w0 * w1, (S)kIzz, (S)(1.0 / kIzz));
     st[F_OMG + 0] += wd0 * dt;
     st[F_OMG + 1] += wd1 * dt;
     st[F_OMG + 2] += wd2 * dt;
@@ -742,8 +820,9 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
 
 template <typename S, int VAR>
 __device__ inline S physics_step(S st[F_N], float4 act, S dt, bool &crash,
-                                 const VarArgs<VAR> *wp = nullptr, bool *reached = nullptr) {
-    return physics_step_mixed<S, VAR>(st, motor_mix(act), dt, crash, wp, reached);
+                                 const VarArgs<VAR> *wp = nullptr, bool *reached = nullptr,
+                                 const Airframe *af = nullptr) {
+    return physics_step_mixed<S, VAR>(st, motor_mix(act), dt, crash, wp, reached, af);
 }
 
 // ---- rk4 variant (DR_VARIANT_RK4) ----
@@ -947,8 +1026,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // (and the gym env on a waypoint course: the gym's step, a target that
     // moves on when it is reached)
     constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
-    constexpr bool GYMSTATE =
-        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND || WAYPT;
+    // (and the gym env on a randomised airframe: the gym's step on the
+    // episode's mass, inertia and motor gains)
+    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 ||
+                              WIND || WAYPT || AIRF;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
@@ -1024,6 +1106,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         wj = *at(p_wp, i);
         wq = *at(p_wp + v.stride, i);
     }
+    // airframe: the episode's six words
+    Airframe af;
+    if constexpr (AIRF) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) af.w[k] = *at(v.mot + k * v.stride, i);
+    }
     if constexpr (TAG) {
         // nothing in the step reads the stored target: a reset writes it
 #pragma unroll
@@ -1085,6 +1173,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         r = rk4_step<S>(st, qd, motor_mix(act), v.dt, rk4_h6<S>(va), crash);
     } else if constexpr (WAYPT) {
         r = physics_step<S, VAR>(st, act, v.dt, crash, &va, &reached);
+    } else if constexpr (AIRF) {
+        // the motor mixes of the gained command, the physics on 1/m and 1/s
+        af.recip();
+        r = physics_step<S, VAR>(st, airframe_gain(af, act), v.dt, crash, nullptr, nullptr, &af);
     } else {
         r = physics_step<S, VAR>(st, act, v.dt, crash);
     }
@@ -1175,6 +1267,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                     for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                 }
                 if constexpr (WAYPT) wj = 0;   // a new course; q counts on
+                if constexpr (AIRF) {
+                    // the new episode's airframe (Philox in host-uniform mode
+                    // too); a reset is the six words' only writer
+                    airframe_draw(v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i),
+                                  ep_old + 1, va, af.w);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) *at(v.mot + k * v.stride, i) = af.w[k];
+                }
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
                 if constexpr (SMOOTH) {
@@ -1306,8 +1406,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     // (and the gym env on a waypoint course: the gym's step, a target that
     // moves on when it is reached)
     constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
-    constexpr bool GYMSTATE =
-        VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 || WIND || WAYPT;
+    // (and the gym env on a randomised airframe: the gym's step on the
+    // episode's mass, inertia and motor gains)
+    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
+    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 ||
+                              WIND || WAYPT || AIRF;
     constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
@@ -1359,6 +1462,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         wj = *at(p_wp, i);
         wq = *at(p_wp + v.stride, i);
     }
+    // airframe: the six words and the two reciprocals, carried in registers
+    // over the launch; a reset redraws them
+    Airframe af;
+    if constexpr (AIRF) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) af.w[k] = *at(v.mot + k * v.stride, i);
+        af.recip();
+    }
     if constexpr (GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
@@ -1398,6 +1509,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     constexpr int NB = VAR == DR_VARIANT_MOVING ? 4 : 1;   // Philox blocks per reset
     u32x4 nd[NB] = {};
     bool nd_ok = false;
+    // (airframe: the next episode's six words and two reciprocals ride with
+    // them, so the branch holds neither their two Philox blocks nor the two
+    // divides; the values are the same either way)
+    Airframe afn;
     // the step limit in a VGPR: under the kernel's SGPR pressure the
     // compiler otherwise re-reads it from the kernel arguments at every
     // step (a scalar load and its wait on the critical path)
@@ -1409,6 +1524,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     // or (smooth) those of the lagged forces, which the lag updates here
     auto mix_of = [&](const float4 act) -> MotorMix {
         if constexpr (SMOOTH) return motor_mix(smooth_filter(act, fm, va.alpha, dev_sq));
+        else if constexpr (AIRF) return motor_mix(airframe_gain(af, act));
         else return motor_mix(act);
     };
     auto step_one = [&](const MotorMix mx, const int t) {
@@ -1420,6 +1536,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                     nd[b] = philox4x32_10(u32x4{(uint32_t)(ep_num + 1), (uint32_t)gid,
                                                 (uint32_t)(gid >> 32), TAG_RESET | (uint32_t)b},
                                           vk.seed_lo, vk.seed_hi);
+                if constexpr (AIRF) {
+                    airframe_draw(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, afn.w);
+                    afn.recip();
+                }
                 nd_ok = true;
             }
         }
@@ -1433,6 +1553,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         if constexpr (RK4) r = rk4_step<S>(st, qd, mx, v.dt, rk4_h6<S>(va), crash);
         else if constexpr (WAYPT)
             r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, &va, &reached);
+        else if constexpr (AIRF)
+            r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, nullptr, nullptr, &af);
         else r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
         bool done;
@@ -1479,6 +1601,14 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 step = 0;
                 reset_any = true;
                 if constexpr (GYMSTATE) {
+                    if constexpr (AIRF) {
+                        if (nd_ok) {
+                            af = afn;
+                        } else {
+                            airframe_draw(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, af.w);
+                            af.recip();
+                        }
+                    }
                     gym_reset_regs(vk, i, 0, st, ep_num, eps, nd_ok ? &nd[0] : nullptr);
                     nd_ok = false;
                     if constexpr (RK4) rk4_reset_quat(st, qd);
@@ -1568,6 +1698,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(wm[k]), "v"(wg[k]));
         }
         if constexpr (WAYPT) asm volatile("" ::"v"(wj), "v"(wq));
+        if constexpr (AIRF) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) asm volatile("" ::"v"(af.w[k]));
+        }
         // Two steps ahead, in two registers that alternate (the loop is
         // unrolled by two so each keeps its role): step t's action was
         // loaded at the top of step t-2; younger than that load are step
@@ -1626,6 +1760,10 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             if constexpr (GYMSTATE) {
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
+                if constexpr (AIRF) {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) *at(v.mot + k * v.stride, i) = af.w[k];
+                }
             } else if constexpr (VAR == DR_VARIANT_MOVING) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) *at(fp.p[F_TGT + k], i) = cen[k];
@@ -2538,6 +2676,22 @@ __global__ void wind_field_kernel(float *wind, int64_t stride, int64_t n, const 
     }
 }
 
+// Airframe: the six words of each env's CURRENT episode (ep_num as stored),
+// for every env (mask null: the enabling dr_set_airframe, dr_reset) or those
+// with mask[i] != 0 (dr_reset_masked).  Runs behind the gym's env_reset_kernel
+// on the same stream, as wind_fill_kernel does.
+__global__ __launch_bounds__(kBlock) void airframe_fill_kernel(
+    float *air, int64_t stride, int64_t n, const int32_t *ep_num, int64_t env_id_offset,
+    uint32_t k0, uint32_t k1, VarArgs<KVAR_AIRFRAME> va, const uint8_t *mask) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (mask && !mask[i]) return;
+    float af[6];
+    airframe_draw(k0, k1, (uint64_t)(env_id_offset + i), ep_num[i], va, af);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) air[k * stride + i] = af[k];
+}
+
 // Waypoints: a new course (j = 0) for every env (mask null: dr_reset) or those
 // with mask[i] != 0 (dr_reset_masked); the reach counter q stays.  Runs behind
 // the gym's env_reset_kernel on the same stream, as wind_fill_kernel does.
@@ -2609,6 +2763,12 @@ struct dr_handle {
     // At most one of `wind` and `wp` is set.
     float reach_radius = 0.0f, reach_bonus = 0.0f;
     int32_t *wp = nullptr;
+    // DR_VARIANT_GYM (dr_set_airframe): the three spreads, passed to each
+    // launch, and the six f32 arrays of `stride` elements (m, s, g0..g3) the
+    // first non-neutral call allocates; while null the handle launches the
+    // gym's kernels.  At most one of `wind`, `wp` and `air` is set.
+    float mass_spread = 0.0f, inertia_spread = 0.0f, motor_spread = 0.0f;
+    float *air = nullptr;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -2647,7 +2807,8 @@ EnvView<S> view_of(const dr_handle *h) {
              h->cfg.variant == DR_VARIANT_RK4)
                 ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
                 : (h->cfg.variant == DR_VARIANT_GYM
-                       ? (h->wp ? reinterpret_cast<float *>(h->wp) : h->wind)
+                       ? (h->wp ? reinterpret_cast<float *>(h->wp)
+                                : (h->air ? h->air : h->wind))
                        : nullptr);
     v.n = h->n;
     v.env_id_offset = h->cfg.env_id_offset;
@@ -2696,6 +2857,8 @@ int with_state(const dr_handle *h, F &&f) {
                 if (h->wind) return f(s, std::integral_constant<int, KVAR_WIND>{});
                 // on a waypoint course: the gym-with-waypoints kernels
                 if (h->wp) return f(s, std::integral_constant<int, KVAR_WAYPOINT>{});
+                // on randomised airframes: the gym-with-airframe kernels
+                if (h->air) return f(s, std::integral_constant<int, KVAR_AIRFRAME>{});
                 return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
             case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
             case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
@@ -2719,6 +2882,8 @@ VarArgs<VAR> var_args(const dr_handle *h) {
     else if constexpr (VAR == KVAR_WIND)
         return VarArgs<VAR>{h->drag, h->gust_b, h->gust_c, h->wind_speed};
     else if constexpr (VAR == KVAR_WAYPOINT) return VarArgs<VAR>{h->reach_radius, h->reach_bonus};
+    else if constexpr (VAR == KVAR_AIRFRAME)
+        return VarArgs<VAR>{h->mass_spread, h->inertia_spread, h->motor_spread};
     else return VarArgs<VAR>{};
 }
 
@@ -2748,6 +2913,20 @@ int launch_wind_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
     return DR_OK;
 }
 
+// The airframe of every env's (mask: the masked envs') current episode,
+// enqueued on `st`.
+int launch_airframe_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
+    const int32_t *ep_num = h->cfg.state_dtype == DR_STATE_F64 ? view_of<double>(h).ep_num
+                                                               : view_of<float>(h).ep_num;
+    hipLaunchKernelGGL(airframe_fill_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->air,
+                       h->stride, h->n, ep_num, h->cfg.env_id_offset, (uint32_t)h->cfg.seed,
+                       (uint32_t)(h->cfg.seed >> 32), var_args<KVAR_AIRFRAME>(h), mask);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string("airframe_fill_kernel: ") + hipGetErrorString(e));
+    return DR_OK;
+}
+
 // A new course (j = 0) for every env (mask: the masked envs), enqueued on `st`.
 int launch_waypoint_restart(dr_handle *h, const uint8_t *mask, hipStream_t st) {
     hipLaunchKernelGGL(waypoint_restart_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->wp,
@@ -2763,15 +2942,21 @@ int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
     return with_state(h, [&](auto s, auto var) {
         // a wind handle resets as the gym does (the wind is not observed),
         // then draws the new episodes' mean wind behind it; a waypoint
-        // handle likewise, then starts the new episodes' courses
+        // handle likewise, then starts the new episodes' courses; an
+        // airframe handle likewise, then draws the new episodes' airframes
         constexpr int V = decltype(var)::value;
-        constexpr int RV = (V == KVAR_WIND || V == KVAR_WAYPOINT) ? (int)DR_VARIANT_GYM : V;
+        constexpr int RV = (V == KVAR_WIND || V == KVAR_WAYPOINT || V == KVAR_AIRFRAME)
+                               ? (int)DR_VARIANT_GYM
+                               : V;
         int rc = launch_reset<typename decltype(s)::type, RV>(h, mask, obs, mode, init, st);
         if constexpr (V == KVAR_WIND) {
             if (rc == DR_OK) rc = launch_wind_fill(h, mask, st);
         }
         if constexpr (V == KVAR_WAYPOINT) {
             if (rc == DR_OK) rc = launch_waypoint_restart(h, mask, st);
+        }
+        if constexpr (V == KVAR_AIRFRAME) {
+            if (rc == DR_OK) rc = launch_airframe_fill(h, mask, st);
         }
         return rc;
     });
@@ -2847,10 +3032,11 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
     // state, the partner exchange and the quaternion step are not built into
     // the warp-specialised forms), whatever the override says.
     // (likewise a gym handle with wind: m and g ride in its registers; and one
-    // on a waypoint course: j and q do)
+    // on a waypoint course: j and q do; and one on randomised airframes: the
+    // six words and two reciprocals do)
     constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG ||
                               VAR == DR_VARIANT_RK4 || VAR == KVAR_WIND ||
-                              VAR == KVAR_WAYPOINT;
+                              VAR == KVAR_WAYPOINT || VAR == KVAR_AIRFRAME;
     const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
@@ -2954,6 +3140,24 @@ int wind_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, flo
     DeviceGuard g(h->cfg.device);
     hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
                        h->wind, h->stride, h->n, ids, k, io, set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return DR_OK;
+}
+
+// DR_FIELD_AIRFRAME of dr_get_state / dr_gather_state / dr_set_state: six f32
+// arrays as the wind's, moved by the same kernel.
+int airframe_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, float *io,
+                   int set, void *stream) {
+    if (!h->air)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    std::string(who) +
+                        ": airframe exists only after a non-neutral dr_set_airframe");
+    if (k == 0) return DR_OK;
+    DeviceGuard g(h->cfg.device);
+    hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
+                       h->air, h->stride, h->n, ids, k, io, set);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -3107,6 +3311,7 @@ int dr_destroy(dr_handle *h) {
         (void)hipFree(h->mem);
         if (h->wind) (void)hipFree(h->wind);
         if (h->wp) (void)hipFree(h->wp);
+        if (h->air) (void)hipFree(h->air);
     }
     delete h;
     return DR_OK;
@@ -3255,6 +3460,9 @@ int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (field == DR_FIELD_WAYPOINT)
         return waypoint_field(h, "dr_get_state", nullptr, h->n, static_cast<int32_t *>(out), 0,
                               stream);
+    if (field == DR_FIELD_AIRFRAME)
+        return airframe_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0,
+                              stream);
     if (int rc = euler_refused(h, "dr_get_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
@@ -3283,6 +3491,9 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
         return wind_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
     if (field == DR_FIELD_WAYPOINT)
         return waypoint_field(h, "dr_gather_state", env_ids, k, static_cast<int32_t *>(out), 0,
+                              stream);
+    if (field == DR_FIELD_AIRFRAME)
+        return airframe_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0,
                               stream);
     if (int rc = euler_refused(h, "dr_gather_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
@@ -3316,6 +3527,9 @@ int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     if (field == DR_FIELD_WAYPOINT)
         return waypoint_field(h, "dr_set_state", nullptr, h->n,
                               const_cast<int32_t *>(static_cast<const int32_t *>(in)), 1, stream);
+    if (field == DR_FIELD_AIRFRAME)
+        return airframe_field(h, "dr_set_state", nullptr, h->n,
+                              const_cast<float *>(static_cast<const float *>(in)), 1, stream);
     if (int rc = euler_refused(h, "dr_set_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
@@ -3416,6 +3630,9 @@ int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma, fl
     // a handle has wind or a waypoint course, not both
     if (h->wp && !neutral)
         return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: the handle is on a waypoint course");
+    // nor wind and randomised airframes
+    if (h->air && !neutral)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: the handle has airframes enabled");
     const bool enable = !h->wind && !neutral;
     float *w = nullptr;
     DeviceGuard g(h->cfg.device);
@@ -3477,6 +3694,8 @@ int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus) {
                     "dr_set_waypoints: only DR_VARIANT_GYM has waypoint courses");
     if (h->wind)
         return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: the handle has wind enabled");
+    if (h->air)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: the handle has airframes enabled");
     // the waypoint counter carries the index, below the step limit, in its
     // low 24 bits
     if (h->cfg.max_steps >= (1 << 24))
@@ -3511,6 +3730,73 @@ int dr_get_waypoints(const dr_handle *h, float *reach_radius, float *reach_bonus
     if (h->cfg.variant != DR_VARIANT_GYM) return DR_ERR_UNSUPPORTED;
     if (reach_radius) *reach_radius = h->reach_radius;
     if (reach_bonus) *reach_bonus = h->reach_bonus;
+    return DR_OK;
+}
+
+int dr_set_airframe(dr_handle *h, float mass_spread, float inertia_spread, float motor_spread) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_airframe: null handle");
+    // written so that NaN fails every test
+    if (!(mass_spread >= 0.0f && mass_spread <= 0.9f))
+        return fail(h, DR_ERR_INVALID, "dr_set_airframe: mass_spread must be in [0, 0.9]");
+    if (!(inertia_spread >= 0.0f && inertia_spread <= 0.9f))
+        return fail(h, DR_ERR_INVALID, "dr_set_airframe: inertia_spread must be in [0, 0.9]");
+    if (!(motor_spread >= 0.0f && motor_spread <= 0.9f))
+        return fail(h, DR_ERR_INVALID, "dr_set_airframe: motor_spread must be in [0, 0.9]");
+    if (h->cfg.variant != DR_VARIANT_GYM)
+        return fail(h, DR_ERR_UNSUPPORTED,
+                    "dr_set_airframe: only DR_VARIANT_GYM has airframe randomisation");
+    // a handle has one of wind, a waypoint course and randomised airframes
+    if (h->wind)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_airframe: the handle has wind enabled");
+    if (h->wp)
+        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_airframe: the handle is on a waypoint course");
+    const bool neutral = mass_spread == 0.0f && inertia_spread == 0.0f && motor_spread == 0.0f;
+    const bool enable = !h->air && !neutral;
+    float *a = nullptr;
+    DeviceGuard g(h->cfg.device);
+    if (enable) {
+        hipError_t e =
+            hipMalloc(reinterpret_cast<void **>(&a), (size_t)6 * h->stride * sizeof(float));
+        if (e != hipSuccess)
+            return fail(h, DR_ERR_NOMEM,
+                        std::string("dr_set_airframe: hipMalloc: ") + hipGetErrorString(e));
+    }
+    const float old[3] = {h->mass_spread, h->inertia_spread, h->motor_spread};
+    h->mass_spread = mass_spread;
+    h->inertia_spread = inertia_spread;
+    h->motor_spread = motor_spread;
+    if (enable) {
+        // every env's current episode gets its airframe now, so that the
+        // field is a function of (key, env, episode) whenever the option was
+        // switched on; the state may be in use on any stream: drain, fill,
+        // drain
+        hipError_t e = hipDeviceSynchronize();
+        h->air = a;
+        int rc = e == hipSuccess ? launch_airframe_fill(h, nullptr, nullptr)
+                                 : fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        if (rc == DR_OK) {
+            e = hipDeviceSynchronize();
+            if (e != hipSuccess) rc = fail(h, DR_ERR_HIP, hipGetErrorString(e));
+        }
+        if (rc != DR_OK) {
+            h->air = nullptr;
+            h->mass_spread = old[0];
+            h->inertia_spread = old[1];
+            h->motor_spread = old[2];
+            (void)hipFree(a);
+            return rc;
+        }
+    }
+    return DR_OK;
+}
+
+int dr_get_airframe(const dr_handle *h, float *mass_spread, float *inertia_spread,
+                    float *motor_spread) {
+    if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_airframe: null handle");
+    if (h->cfg.variant != DR_VARIANT_GYM) return DR_ERR_UNSUPPORTED;
+    if (mass_spread) *mass_spread = h->mass_spread;
+    if (inertia_spread) *inertia_spread = h->inertia_spread;
+    if (motor_spread) *motor_spread = h->motor_spread;
     return DR_OK;
 }
 

@@ -40,7 +40,7 @@ CRASH_PENALTY = 0.0
 
 _VEC_FIELDS = ("pos", "vel", "euler", "omega", "target")
 # (N, width) f32 fields a single variant owns
-_F32_ROW_FIELDS = {"motion": 9, "motor": 4, "wind": 6}
+_F32_ROW_FIELDS = {"motion": 9, "motor": 4, "wind": 6, "airframe": 6}
 # (N, width) i32 fields
 _I32_ROW_FIELDS = {"waypoint": 2}
 # dr_set_waypoints' defaults where only one of the two values is given
@@ -149,6 +149,33 @@ def check_waypoints(variant: str, reach_radius=None, reach_bonus=None,
     return r, b
 
 
+def check_airframe(variant: str, mass_spread=0.0, inertia_spread=0.0, motor_spread=0.0, *,
+                   wind=None, waypoints=None) -> tuple[float, float, float]:
+    """The argument rules of dr_set_airframe, raised as
+    ValueError before any device work: each spread finite and in [0, 0.9] in
+    f32, all three at 0 on every variant but "gym", and, where any is not 0,
+    `wind` (the four dr_set_wind values, if given) all zero and `waypoints`
+    (check_waypoints' result, if given) None.  Returns the three values as the
+    kernels see them (rounded to f32)."""
+    names = ("mass_spread", "inertia_spread", "motor_spread")
+    vals = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for name, x in zip(names, (mass_spread, inertia_spread, motor_spread)):
+            v = float(np.float32(x))
+            if not (0.0 <= v <= float(np.float32(0.9))):
+                raise ValueError(f"{name} must be in [0, 0.9], got {x!r}")
+            vals.append(v)
+    if any(vals):
+        if variant != "gym":
+            raise ValueError("mass_spread / inertia_spread / motor_spread need variant='gym', "
+                             f"not {variant!r}")
+        if wind is not None and any(float(w) != 0.0 for w in wind):
+            raise ValueError("a gym env has wind or randomised airframes, not both")
+        if waypoints is not None:
+            raise ValueError("a gym env has a waypoint course or randomised airframes, not both")
+    return tuple(vals)
+
+
 def check_tag(variant: str, tag_radius, crash_penalty, num_envs: int | None = None,
               env_id_offset: int = 0) -> tuple[float, float]:
     """The argument rules of the "tag" variant (dr_create / dr_set_tag), raised
@@ -219,6 +246,14 @@ class DroneBatch:
                option with the other at its default (0.25 / 1.0), and with it
                the "waypoint" field ((N,2) i32: index within the episode,
                reaches since enabling).  Not together with wind.
+    mass_spread, inertia_spread, motor_spread
+               "gym" only: per-episode airframe
+               randomisation.  Each episode draws a mass scale m in
+               1 +- mass_spread, an inertia scale s in 1 +- inertia_spread and
+               four motor gains in 1 +- motor_spread, each spread in [0, 0.9].
+               All neutral at 0; the airframe is not observed.  Any non-zero
+               value enables the "airframe" field ((N,6) f32: m, s, g0..g3).
+               Not together with wind or a waypoint course.
     """
 
     def __init__(self, num_envs: int, variant: str = "gym",
@@ -230,12 +265,16 @@ class DroneBatch:
                  tag_radius: float | None = None, crash_penalty: float | None = None,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
                  gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None):
+                 reach_radius: float | None = None, reach_bonus: float | None = None,
+                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
+                 motor_spread: float = 0.0):
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
         check_smoothing(variant, motor_alpha, rate_penalty)
         wind = check_wind(variant, drag, wind_speed, gust_sigma, gust_rate, max_steps)
         course = check_waypoints(variant, reach_radius, reach_bonus, max_steps, wind)
+        airframe = check_airframe(variant, mass_spread, inertia_spread, motor_spread,
+                                  wind=wind, waypoints=course)
         tag_radius, crash_penalty = check_tag(variant, tag_radius, crash_penalty, num_envs,
                                               env_id_offset)
         if dtype not in (torch.float64, torch.float32):
@@ -288,10 +327,14 @@ class DroneBatch:
         self.wind_enabled = False
         self.reach_radius = self.reach_bonus = 0.0
         self.waypoints_enabled = False
+        self.mass_spread = self.inertia_spread = self.motor_spread = 0.0
+        self.airframe_enabled = False
         if any(wind):
             self.set_wind(*wind)
         if course is not None:
             self.set_waypoints(*course)
+        if any(airframe):
+            self.set_airframe(*airframe)
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -594,6 +637,8 @@ class DroneBatch:
         w = check_wind(self.variant, drag, wind_speed, gust_sigma, gust_rate, self.max_steps)
         if self.waypoints_enabled and any(w):
             raise ValueError("a gym env has wind or a waypoint course, not both")
+        if self.airframe_enabled and any(w):
+            raise ValueError("a gym env has wind or randomised airframes, not both")
         check(self.L.dr_set_wind(self.handle, *w), self.handle)
         self.drag, self.wind_speed, self.gust_sigma, self.gust_rate = w
         self.wind_enabled = self.wind_enabled or any(w)
@@ -613,9 +658,32 @@ class DroneBatch:
             reach_radius = REACH_RADIUS
         rb = check_waypoints(self.variant, reach_radius, reach_bonus, self.max_steps,
                              (1.0,) if self.wind_enabled else None)
+        if self.airframe_enabled:
+            raise ValueError("a gym env has a waypoint course or randomised airframes, not both")
         check(self.L.dr_set_waypoints(self.handle, *rb), self.handle)
         self.reach_radius, self.reach_bonus = rb
         self.waypoints_enabled = True
+
+    def set_airframe(self, mass_spread: float = 0.0, inertia_spread: float = 0.0,
+                     motor_spread: float = 0.0) -> None:
+        """variant="gym": per-episode airframe randomisation (dr_set_airframe,
+        DESIGN.md section 19).  The spreads apply from each env's next reset
+        (resets are their only readers).  The first call with a non-zero
+        value allocates the "airframe" field and draws every env's airframe
+        for its current episode: it waits for the device and must not be made
+        while a graph is being captured (a captured graph keeps the kernels
+        and values it was captured with).  All zeros on a batch that never
+        enabled the option enables nothing."""
+        if self.variant != "gym":
+            raise ValueError(f"set_airframe needs variant='gym', not {self.variant!r}")
+        a = check_airframe(self.variant, mass_spread, inertia_spread, motor_spread,
+                           wind=(1.0,) if self.wind_enabled else None,
+                           waypoints=(0.0, 0.0) if self.waypoints_enabled else None)
+        if (self.wind_enabled or self.waypoints_enabled) and not any(a):
+            return   # neutral on a handle that carries another option: nothing to do
+        check(self.L.dr_set_airframe(self.handle, *a), self.handle)
+        self.mass_spread, self.inertia_spread, self.motor_spread = a
+        self.airframe_enabled = self.airframe_enabled or any(a)
 
     def set_reset_uniforms(self, u) -> None:
         """rng='host': (N,5) f64 uniforms ((N,14) for "moving") consumed by

@@ -114,16 +114,26 @@ class PPOConfig:
     # option with the other at its default (0.25 / 1.0).  Not together with wind
     reach_radius: float | None = None
     reach_bonus: float | None = None
+    # variant "gym" only: per-episode airframe
+    # randomisation, the half-widths in [0, 0.9] of the mass scale, the
+    # inertia scale and the four motor gains around 1.  All neutral at 0; the
+    # policy does not observe the airframe.  Not together with wind or a course
+    mass_spread: float = 0.0
+    inertia_spread: float = 0.0
+    motor_spread: float = 0.0
 
     def __post_init__(self):
-        from .env import OBS_DIM, check_smoothing, check_tag, check_waypoints, check_wind
+        from .env import (OBS_DIM, check_airframe, check_smoothing, check_tag, check_waypoints,
+                          check_wind)
         if self.variant not in OBS_DIM:
             raise ValueError(f"unknown variant {self.variant!r}")
         check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
         check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
         wind = check_wind(self.variant, self.drag, self.wind_speed, self.gust_sigma,
                           self.gust_rate)
-        check_waypoints(self.variant, self.reach_radius, self.reach_bonus, wind=wind)
+        course = check_waypoints(self.variant, self.reach_radius, self.reach_bonus, wind=wind)
+        check_airframe(self.variant, self.mass_spread, self.inertia_spread, self.motor_spread,
+                       wind=wind, waypoints=course)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -158,7 +168,9 @@ class PPOTrainer:
                               tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty,
                               drag=cfg.drag, wind_speed=cfg.wind_speed,
                               gust_sigma=cfg.gust_sigma, gust_rate=cfg.gust_rate,
-                              reach_radius=cfg.reach_radius, reach_bonus=cfg.reach_bonus)
+                              reach_radius=cfg.reach_radius, reach_bonus=cfg.reach_bonus,
+                              mass_spread=cfg.mass_spread, inertia_spread=cfg.inertia_spread,
+                              motor_spread=cfg.motor_spread)
         # waypoint courses: the reaches of the last rollout (device scalar)
         self._wp_gain = None
         if cfg.initial_eps:
@@ -357,6 +369,7 @@ class PPOTrainer:
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
                     e.wind_enabled, e.drag, e.wind_speed, e.gust_sigma, e.gust_rate,
                     e.waypoints_enabled, e.reach_radius, e.reach_bonus,
+                    e.airframe_enabled, e.mass_spread, e.inertia_spread, e.motor_spread,
                     self.env.tag_radius, self.env.crash_penalty,
                     self.env.motor_alpha, self.env.rate_penalty)
         o = self.opt
@@ -634,7 +647,8 @@ class PPOTrainer:
         return self._ENV_FIELDS + {"moving": ("motion",),
                                    "smooth": ("motor",)}.get(self.cfg.variant, ()) + \
             (("wind",) if self.env.wind_enabled else ()) + \
-            (("waypoint",) if self.env.waypoints_enabled else ())
+            (("waypoint",) if self.env.waypoints_enabled else ()) + \
+            (("airframe",) if self.env.airframe_enabled else ())
 
     def state_dict(self):
         """Everything needed to resume bit-for-bit on the same device count:
@@ -675,6 +689,10 @@ class PPOTrainer:
                 # likewise a waypoint checkpoint: the checkpoint's course
                 self.env.set_waypoints(sd["config"].get("reach_radius"),
                                        sd["config"].get("reach_bonus"))
+            if "airframe" in sd["env"] and not self.env.airframe_enabled:
+                # likewise an airframe checkpoint: the checkpoint's spreads
+                self.env.set_airframe(*(sd["config"].get(k, 0.0) for k in
+                                        ("mass_spread", "inertia_spread", "motor_spread")))
             for k, v in sd["env"].items():
                 self.env.set(k, v)
             self.obs[0].copy_(sd["last_obs"].to(self.device))

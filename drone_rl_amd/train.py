@@ -88,6 +88,12 @@ def main(argv=None):
     ap.add_argument("--reach-bonus", type=float, default=None,
                     help="--variant gym: reward added in the step of a reach (default 1.0 "
                          "when only --reach-radius is given)")
+    ap.add_argument("--mass-spread", type=float, default=0.0,
+                    help="--variant gym: per-episode mass scale drawn in 1 +- this, in [0, 0.9]")
+    ap.add_argument("--inertia-spread", type=float, default=0.0,
+                    help="--variant gym: per-episode inertia scale drawn in 1 +- this")
+    ap.add_argument("--motor-spread", type=float, default=0.0,
+                    help="--variant gym: per-episode gain of each motor drawn in 1 +- this")
     ap.add_argument("--sb3-defaults", action="store_true",
                     help="SB3 PPO defaults of the reference (n_steps 2048, batch 64, 64x64)")
     ap.add_argument("--checkpoint", default="./dd_gpu.pt")
@@ -127,6 +133,8 @@ def main(argv=None):
                   drag=a.drag, wind_speed=a.wind_speed, gust_sigma=a.gust_sigma,
                   gust_rate=a.gust_rate,
                   reach_radius=a.reach_radius, reach_bonus=a.reach_bonus,
+                  mass_spread=a.mass_spread, inertia_spread=a.inertia_spread,
+                  motor_spread=a.motor_spread,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

@@ -37,8 +37,10 @@ except Exception:  # noqa: BLE001 - SB3 absent (this image)
 # "motor": the smooth variant's motor forces; "quat": the rk4 variant's
 # attitude (DroneBatch raises on the others); "wind": a gym batch's mean wind
 # and gust once wind is enabled; "waypoint": a gym batch's (index, reaches)
-# on a waypoint course
-_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat", "wind", "waypoint")
+# on a waypoint course; "airframe": a gym batch's (m, s, g0..g3) once airframe
+# randomisation is enabled
+_STATE = ("pos", "vel", "euler", "omega", "target", "motor", "quat", "wind", "waypoint",
+          "airframe")
 _SCALAR = {"current_step": int, "ep_num": int, "eps": float}
 
 
@@ -55,7 +57,9 @@ class BatchedDroneVecEnv(_VecEnvBase):
                  tag_radius: float | None = None, crash_penalty: float | None = None,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
                  gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None):
+                 reach_radius: float | None = None, reach_bonus: float | None = None,
+                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
+                 motor_spread: float = 0.0):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
@@ -65,7 +69,9 @@ class BatchedDroneVecEnv(_VecEnvBase):
                                 rate_penalty=rate_penalty, tag_radius=tag_radius,
                                 crash_penalty=crash_penalty, drag=drag, wind_speed=wind_speed,
                                 gust_sigma=gust_sigma, gust_rate=gust_rate,
-                                reach_radius=reach_radius, reach_bonus=reach_bonus)
+                                reach_radius=reach_radius, reach_bonus=reach_bonus,
+                                mass_spread=mass_spread, inertia_spread=inertia_spread,
+                                motor_spread=motor_spread)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -140,6 +146,15 @@ class BatchedDroneVecEnv(_VecEnvBase):
             raise AttributeError("attribute 'wind' needs a 'gym' batch with wind enabled")
         if attr_name == "waypoint" and not self.batch.waypoints_enabled:
             raise AttributeError("attribute 'waypoint' needs a 'gym' batch on a waypoint course")
+        if attr_name == "airframe" and not self.batch.airframe_enabled:
+            raise AttributeError("attribute 'airframe' needs a 'gym' batch with airframe "
+                                 "randomisation enabled")
+        if attr_name in ("mass", "I") and self.batch.airframe_enabled:
+            # each env's own vehicle this episode: MASS m, INERTIA s
+            af = self.batch.get_host("airframe")
+            if attr_name == "mass":
+                return [MASS * float(af[i, 0]) for i in idx]
+            return [np.array(INERTIA) * float(af[i, 1]) for i in idx]
         if attr_name in _STATE:
             v = self.batch.get_host(attr_name)
             return [v[i].copy() for i in idx]
@@ -217,7 +232,9 @@ class DroneVectorEnv:
                  motor_alpha: float = 1.0, rate_penalty: float = 0.0,
                  drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
                  gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None):
+                 reach_radius: float | None = None, reach_bonus: float | None = None,
+                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
+                 motor_spread: float = 0.0):
         if variant not in ("gym", "smooth", "rk4"):
             raise ValueError("DroneVectorEnv wraps the 'gym', 'smooth' or 'rk4' variant")
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
@@ -225,7 +242,8 @@ class DroneVectorEnv:
                                 motor_alpha=motor_alpha, rate_penalty=rate_penalty,
                                 drag=drag, wind_speed=wind_speed, gust_sigma=gust_sigma,
                                 gust_rate=gust_rate, reach_radius=reach_radius,
-                                reach_bonus=reach_bonus)
+                                reach_bonus=reach_bonus, mass_spread=mass_spread,
+                                inertia_spread=inertia_spread, motor_spread=motor_spread)
         self.num_envs = num_envs
         od = self.batch.obs_dim
         self.single_observation_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -267,9 +285,16 @@ class DroneVectorEnv:
     def get_attr(self, name: str):
         """A state field of every env as one (N, ...) array; "waypoint" (the
         index within the episode, the reaches since enabling) on a waypoint
-        course."""
+        course; "airframe" (m, s, g0..g3) with airframe randomisation enabled,
+        and then "mass" (N,) and "I" (N,3), each env's own this episode."""
         if name == "waypoint" and not self.batch.waypoints_enabled:
             raise AttributeError("attribute 'waypoint' needs a batch on a waypoint course")
+        if name == "airframe" and not self.batch.airframe_enabled:
+            raise AttributeError("attribute 'airframe' needs a batch with airframe "
+                                 "randomisation enabled")
+        if name in ("mass", "I") and self.batch.airframe_enabled:
+            af = self.batch.get_host("airframe").astype(np.float64)
+            return MASS * af[:, 0] if name == "mass" else af[:, 1:2] * np.array(INERTIA)
         if name not in _STATE and name not in _SCALAR:
             raise AttributeError(f"DroneVectorEnv has no attribute {name!r}")
         return self.batch.get_host(name)

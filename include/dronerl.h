@@ -133,10 +133,15 @@ enum dr_field {   /* dr_get_state / dr_set_state, all device buffers      */
     DR_FIELD_WIND = 13,     /* (N,6) f32  gym variant after a non-neutral
                                dr_set_wind: the episode's mean wind xyz, the
                                gust xyz (m/s); DR_ERR_UNSUPPORTED before      */
-    DR_FIELD_WAYPOINT = 14  /* (N,2) i32  gym variant after dr_set_waypoints:
+    DR_FIELD_WAYPOINT = 14, /* (N,2) i32  gym variant after dr_set_waypoints:
                                j, the current waypoint's index within the
                                episode, and q, the reaches since enabling;
                                DR_ERR_UNSUPPORTED before                      */
+    DR_FIELD_AIRFRAME = 15  /* (N,6) f32  gym variant after a non-neutral
+                               dr_set_airframe: the episode's mass scale m,
+                               inertia scale s, motor gains g0..g3; a written
+                               m or s that is not positive and finite is the
+                               caller's error; DR_ERR_UNSUPPORTED before      */
 };
 
 typedef struct dr_config {
@@ -344,6 +349,54 @@ int dr_get_wind(const dr_handle *h, float *drag, float *wind_speed, float *gust_
    pointer may be NULL). */
 int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus);
 int dr_get_waypoints(const dr_handle *h, float *reach_radius, float *reach_bonus);
+
+/* DR_VARIANT_GYM: per-episode airframe randomisation,
+   an option of the gym env.  Each spread is finite and in [0, 0.9]; all three
+   are neutral at 0:
+     mass_spread     sigma_m, half-width of the mass scale m around 1
+     inertia_spread  sigma_I, half-width of the inertia scale s around 1
+     motor_spread    sigma_g, half-width of each motor gain g_j around 1
+   The vehicle of an episode has mass m * 1 kg, inertia s * (0.005, 0.005,
+   0.01) and motors that deliver g_j times their command.  Per env six f32
+   words are state (DR_FIELD_AIRFRAME): m, s, g0..g3.  With (key, counter) ->
+   Philox4x32-10 block under the handle's seed, gid the global env id and
+   xi = f32(2 u - 1) of a word's uniform u = w * 2^-32 (exact in f64, one
+   rounding):
+     reset into episode ep:  m = 1.0f + sigma_m * xi of word 0 and
+       s = 1.0f + sigma_I * xi of word 1 of the block of counter
+       (ep, gid_lo, gid_hi, 0x46000000 | 0); g_j = 1.0f + sigma_g * xi_j of the
+       four words of block 0x46000000 | 1; every operation one f32 rounding; in
+       DR_RNG_HOST_UNIFORMS mode too (the host buffer keeps its (N,5) meaning)
+     step, S the state scalar, everything not named here the gym's:
+       a'_j = g_j * a_j (f32), and the gym's motor mixes are taken on a';
+       im = 1.0f / m, is = 1.0f / s (IEEE f32 divides);
+       the three accelerations use (r_k2 * T) * (S)im where the gym has
+       (r_k2 * T) / (S)mass;
+       tau_phi = ((S)factor * (S)mix_phi) * (S)is, likewise theta, and the yaw
+       torque is (S)(k_yaw * mix_psi) * (S)is.  One common inertia scale leaves
+       the gyroscopic terms unchanged, so only the torques scale.
+   At m = s = g = 1 every inserted product is by exactly 1 and the step is the
+   gym's bit for bit.  The observation stays the gym's 15 floats: the airframe
+   is not observed.
+   The first non-neutral call allocates the six arrays and fills them for
+   every env's CURRENT episode (so the field is a function of key, env and
+   episode whenever the option was switched on): that call is synchronous (it
+   waits for the device) and must not be made during graph capture.  Until
+   then the handle allocates nothing more and launches exactly the gym's
+   kernels; afterwards it launches the airframe kernels, also at all-zero
+   spreads.  Later calls change the spreads only, which apply from each env's
+   next reset (resets are their only readers).  dr_reset and dr_reset_masked
+   redraw the field of the rows they reset.  dr_rollout* on such a handle runs
+   the one-role kernel at every size and is bitwise k dr_step calls.
+   DR_ERR_INVALID for a null handle or a value that is not in [0, 0.9] (NaN
+   included); DR_ERR_UNSUPPORTED on the other variants and on a handle with
+   wind or waypoints enabled; on an airframe handle a non-neutral dr_set_wind
+   and any dr_set_waypoints are DR_ERR_UNSUPPORTED.  A refused call changes
+   nothing.  dr_get_airframe reads the three values back (any pointer may be
+   NULL).  These additions break no caller: DR_ABI_VERSION stays 16. */
+int dr_set_airframe(dr_handle *h, float mass_spread, float inertia_spread, float motor_spread);
+int dr_get_airframe(const dr_handle *h, float *mass_spread, float *inertia_spread,
+                    float *motor_spread);
 
 /* Synthetic random policy: out (n,4) f32 i.i.d. U[lo,hi) from Philox keyed
    by seed with counter (env_id_offset + i, step).  Not part of the

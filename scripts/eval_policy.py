@@ -37,9 +37,18 @@ flies a course and a course policy flies the plain gym env
 result adds waypoints_per_episode, the reach counters' sum over the episodes
 that ended.
 
+A gym checkpoint is flown on randomised airframes
+with --mass-spread / --inertia-spread / --motor-spread; a flag not given takes
+the checkpoint's value (0 for checkpoints from before the option).  The
+airframe is not observed, so any gym policy can be put on any airframe.
+--fixed-airframe m,s,g0,g1,g2,g3 flies every env and every episode on that one
+airframe instead (written through set("airframe") ahead of each step).
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
                                 [--drag 0.5 --wind-speed 2 --gust-sigma 0.5 --gust-rate 0.1]
                                 [--reach-radius 0.25 --reach-bonus 1]
+                                [--mass-spread 0.3 --inertia-spread 0.3 --motor-spread 0.1]
+                                [--fixed-airframe 1.3,1,0.9,1,1,1]
 """
 import argparse
 import json
@@ -52,8 +61,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import (HOVER, MOTOR_MAX, OBS_DIM, check_tag, check_waypoints,  # noqa: E402
-                              check_wind)
+from drone_rl_amd.env import (HOVER, MOTOR_MAX, OBS_DIM, check_airframe, check_tag,  # noqa: E402
+                              check_waypoints, check_wind)
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
@@ -64,6 +73,15 @@ def wind_of(cfg, args):
     """The four wind values: the command line's, else the checkpoint's."""
     return tuple(float(cfg.get(k, 0.0)) if getattr(args, k) is None else getattr(args, k)
                  for k in WIND_KEYS)
+
+
+AIRFRAME_KEYS = ("mass_spread", "inertia_spread", "motor_spread")
+
+
+def airframe_of(cfg, args):
+    """The three spreads: the command line's, else the checkpoint's."""
+    return tuple(float(cfg.get(k, 0.0)) if getattr(args, k) is None else getattr(args, k)
+                 for k in AIRFRAME_KEYS)
 
 
 def course_of(cfg, args):
@@ -78,7 +96,7 @@ def course_of(cfg, args):
 
 @torch.no_grad()
 def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0),
-             course=(None, None)):
+             course=(None, None), airframe=(0.0, 0.0, 0.0), fixed_airframe=None):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -92,7 +110,15 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     pol.flat.data.copy_(sd["flat"].to(dev))
     env = DroneBatch(envs, variant, device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
                      motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND_KEYS, wind)),
-                     reach_radius=course[0], reach_bonus=course[1])
+                     reach_radius=course[0], reach_bonus=course[1],
+                     **dict(zip(AIRFRAME_KEYS, airframe)))
+    fixed = None
+    if fixed_airframe is not None:
+        # one airframe for every env and episode: the option enabled, its
+        # resets drawing ones, the field written again ahead of each step
+        env.set_airframe(0.5, 0.5, 0.5)
+        env.set_airframe(0.0, 0.0, 0.0)
+        fixed = torch.tensor(fixed_airframe, dtype=torch.float32, device=dev).repeat(envs, 1)
     env.set("eps", torch.full((envs,), float(eps), dtype=torch.float64))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
@@ -114,6 +140,8 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
         if smooth:
             force = obs[:, 15:19]
         dev_sq += float(((cmd - force) ** 2).sum(1).mean())
+        if fixed is not None:
+            env.set("airframe", fixed)
         o, r, d = env.step(cmd)
         obs = o.clone()
         db = d.bool()
@@ -205,6 +233,13 @@ def main():
                          "(default: the checkpoint's; 0 = the plain gym env)")
     ap.add_argument("--reach-bonus", type=float, default=None,
                     help="gym checkpoints: the reward added in the step of a reach")
+    for k in AIRFRAME_KEYS:
+        ap.add_argument("--" + k.replace("_", "-"), type=float, default=None,
+                        help="gym checkpoints: fly on airframes drawn with this spread "
+                             "(default: the checkpoint's)")
+    ap.add_argument("--fixed-airframe", default=None,
+                    help="gym checkpoints: m,s,g0,g1,g2,g3 -- fly every episode on this one "
+                         "airframe (not together with the spreads)")
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
     cfg = torch.load(a.ckpt, map_location="cpu", weights_only=True)["config"]
@@ -224,10 +259,28 @@ def main():
     rb = check_waypoints(out["variant"], *course, wind=wind)
     if rb is not None:
         out["reach_radius"], out["reach_bonus"] = rb
+    fixed = None
+    if a.fixed_airframe is not None:
+        fixed = [float(x) for x in a.fixed_airframe.split(",")]
+        if len(fixed) != 6 or not (0 < fixed[0] < float("inf") and 0 < fixed[1] < float("inf")):
+            ap.error("--fixed-airframe takes m,s,g0,g1,g2,g3 with m, s positive and finite")
+        if any(getattr(a, k) for k in AIRFRAME_KEYS):
+            ap.error("--fixed-airframe and the spreads exclude each other")
+    airframe = (0.0, 0.0, 0.0) if fixed is not None else airframe_of(cfg, a)
+    if any(airframe) or fixed is not None or out["variant"] == "gym":
+        # raises for a non-gym checkpoint with a spread, or a spread beside
+        # wind or a course
+        out.update(zip(AIRFRAME_KEYS,
+                       check_airframe(out["variant"], *(airframe if fixed is None else (0.5,) * 3),
+                                      wind=wind, waypoints=rb)))
+        if fixed is not None:
+            out.update(zip(AIRFRAME_KEYS, (0.0, 0.0, 0.0)))
+            out["fixed_airframe"] = fixed
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (
             evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det) if out["variant"] == "tag"
-            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind, course))
+            else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind, course, airframe,
+                          fixed))
     print(json.dumps(out), flush=True)
 
 
