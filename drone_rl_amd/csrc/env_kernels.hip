@@ -421,19 +421,59 @@ constexpr int KVAR_WAYPOINT = 65;
 // three options exclude each other pairwise on a handle.
 constexpr int KVAR_AIRFRAME = 66;
 
-// ---- smooth-control variant (DR_VARIANT_SMOOTH; DESIGN.md section 14) ----
-// Observation width of a variant.
+// What the kernels and the host ask about a variant, in one place (DESIGN.md
+// section 20).  One line per variant:
+//   vectorized  no stored target, no per-env reset, 12 obs floats
+//   gym         the reference env: stored target, curriculum reset
+//   moving      the gym's reset plus a target on a Lissajous path: centre and
+//               9 motion words beside the state, 3 more obs floats
+//   smooth      the gym env behind a motor lag: 4 force words, 4 obs floats
+//   tag         gym drones in pairs; the gym's target carried unread, 7 obs
+//               floats past the first 12 from the partner, no words of its own
+//   rk4         the gym's task on a quaternion state and an RK4 step: one
+//               more word of S, 1 more obs float
+//   wind        the gym's step behind a disturbance: 6 words, no obs float
+//   waypoint    the gym's step, a target that moves on when reached: 2 words
+//   airframe    the gym's step on the episode's mass, inertia and motor
+//               gains: 6 words
 template <int VAR>
-constexpr int od_of() {
-    return (VAR == DR_VARIANT_GYM || VAR == KVAR_WIND || VAR == KVAR_WAYPOINT ||
-            VAR == KVAR_AIRFRAME)
-               ? 15
-               : (VAR == DR_VARIANT_MOVING
-                      ? 18
-                      : ((VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG)
-                             ? 19
-                             : (VAR == DR_VARIANT_RK4 ? 16 : 12)));
-}
+struct Traits {
+    static constexpr bool VEC = VAR == DR_VARIANT_VECTORIZED;
+    static constexpr bool MOVING = VAR == DR_VARIANT_MOVING;
+    static constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
+    static constexpr bool TAG = VAR == DR_VARIANT_TAG;
+    static constexpr bool RK4 = VAR == DR_VARIANT_RK4;
+    static constexpr bool WIND = VAR == KVAR_WIND;
+    static constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
+    static constexpr bool AIRF = VAR == KVAR_AIRFRAME;
+    // a gym handle with one of its options enabled
+    static constexpr bool OPTION = WIND || WAYPT || AIRF;
+    // per-env episodes, curriculum and reset draws
+    static constexpr bool GYMLIKE = !VEC;
+    // the gym's stored target and reset
+    static constexpr bool GYMSTATE = GYMLIKE && !MOVING;
+    // observation width
+    static constexpr int OD = MOVING ? 18 : (SMOOTH || TAG) ? 19 : RK4 ? 16 : VEC ? 12 : 15;
+    // Philox blocks per reset
+    static constexpr int NB = MOVING ? 4 : 1;
+    // carries side words in a Side (below); moving's, smooth's and wind's
+    // are locals of the kernels
+    static constexpr bool SIDE = RK4 || WAYPT || AIRF;
+    // its side state's reset is a pure draw, made ahead with the reset's blocks
+    static constexpr bool SIDE_AHEAD = AIRF;
+    // host: the rollout has the one-role kernel only (the side state and the
+    // partner exchange are not built into the warp-specialised forms)
+    static constexpr bool ONE_ROLE = SMOOTH || TAG || RK4 || OPTION;
+    // host: an option resets as the gym does, then refills its words
+    static constexpr int RESET_VAR = OPTION ? (int)DR_VARIANT_GYM : VAR;
+    // host: bytes per env behind the monitor counters (Layout::mot)
+    template <typename S>
+    static constexpr size_t mot_bytes() {
+        return MOVING ? 9 * sizeof(float) : SMOOTH ? 4 * sizeof(float) : RK4 ? sizeof(S) : 0;
+    }
+};
+
+// ---- smooth-control variant (DR_VARIANT_SMOOTH; DESIGN.md section 14) ----
 // What a variant's kernels take beyond the shared arguments: nothing, or the
 // smooth / tag variant's two parameters.  A trailing kernel argument of its own, so
 // the argument blocks of the other variants' kernels stay as they were.
@@ -658,9 +698,10 @@ __device__ inline S tag_reward(const S st[F_N], const S pp[3], float radius, boo
 // smooth: the motor forces, 4); tag: the 7 floats past the first 12
 // (tag_ext).
 template <typename S, int VAR>
-__device__ inline void make_obs(const S st[F_N], float ob[od_of<VAR>()],
+__device__ inline void make_obs(const S st[F_N], float ob[Traits<VAR>::OD],
                                 const float *ext = nullptr) {
-    if constexpr (VAR == DR_VARIANT_RK4) {
+    using T = Traits<VAR>;
+    if constexpr (T::RK4) {
         // p, v, q = (a, b, c, d), omega, target - p; ext[0] = f32(d)
 #pragma unroll
         for (int k = 0; k < 9; ++k) ob[k] = (float)st[k];
@@ -674,18 +715,18 @@ __device__ inline void make_obs(const S st[F_N], float ob[od_of<VAR>()],
     // _get_obs: f32(concat(pos, vel, euler, omega[, target - pos]))  (79)
 #pragma unroll
     for (int k = 0; k < 12; ++k) ob[k] = (float)st[k];
-    if constexpr (VAR == DR_VARIANT_TAG) {
+    if constexpr (T::TAG) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) ob[12 + k] = ext[k];
-    } else if constexpr (VAR != DR_VARIANT_VECTORIZED) {
+    } else if constexpr (!T::VEC) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) ob[12 + k] = (float)(st[F_TGT + k] - st[F_POS + k]);
     }
-    if constexpr (VAR == DR_VARIANT_MOVING) {
+    if constexpr (T::MOVING) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) ob[15 + k] = ext[k];
     }
-    if constexpr (VAR == DR_VARIANT_SMOOTH) {
+    if constexpr (T::SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) ob[15 + k] = ext[k];
     }
@@ -713,14 +754,14 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
                                        const VarArgs<VAR> *wp = nullptr,
                                        bool *reached = nullptr,
                                        const Airframe *af = nullptr) {
-    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
+    using TR = Traits<VAR>;
     // thrust / torques (drone.py:106, 113-117): f32 sums, f64 factor product,
     // the yaw torque stays f32.
     const float thr = mx.thr;
     S tau_phi = (S)kFactor * (S)mx.phi;
     S tau_theta = (S)kFactor * (S)mx.theta;
     const float tau_psi = kKyaw32 * mx.psi;
-    if constexpr (AIRF) {
+    if constexpr (TR::AIRF) {
         // inertia s (Ixx, Iyy, Izz): one common scale leaves the gyroscopic
         // terms as they are, so only the torques scale (the yaw torque below)
         tau_phi = tau_phi * (S)af->is;
@@ -739,7 +780,7 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     const S r22 = cth * cph;
     const S T = (S)thr;
     S acc0, acc1, acc2;
-    if constexpr (AIRF) {
+    if constexpr (TR::AIRF) {
         // mass m kMass: the reciprocal's product where the gym divides
         acc0 = (S)0 + (r02 * T) * (S)af->im;
         acc1 = (S)0 + (r12 * T) * (S)af->im;
@@ -762,7 +803,7 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     const S sec = (S)1 / cth;        // the only IEEE divide; also vd:116
     const S tth = div_rcp(sth, cth, sec);
     S ed2;
-    if constexpr (VAR != DR_VARIANT_VECTORIZED) {
+    if constexpr (!TR::VEC) {
         ed2 = ((S)0 * w0 + div_rcp(sph, cth, sec) * w1) +
               div_rcp(cph, cth, sec) * w2;                             // (184)
     } else {
@@ -778,7 +819,7 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     const S wd0 = div_rcp(tau_phi - (S)(kIyy - kIzz) * w1 * w2, (S)kIxx, (S)(1.0 / kIxx));
     const S wd1 = div_rcp(tau_theta - (S)(kIzz - kIxx) * w0 * w2, (S)kIyy, (S)(1.0 / kIyy));
     S tau_psi_s;
-    if constexpr (AIRF) tau_psi_s = (S)tau_psi * (S)af->is;
+    if constexpr (TR::AIRF) tau_psi_s = (S)tau_psi * (S)af->is;
     else tau_psi_s = (S)tau_psi;
     const S wd2 = div_rcp(tau_psi_s - (S)(kIxx - kIyy) * w0 * w1, (S)kIzz, (S)(1.0 / kIzz));
     st[F_OMG + 0] += wd0 * dt;
@@ -789,18 +830,18 @@ __device__ inline S physics_step_mixed(S st[F_N], MotorMix mx, S dt, bool &crash
     // The tag variant's reward needs the partner's new position: the caller
     // forms it (tag_reward) after the exchange.
     S r = (S)0;
-    if constexpr (VAR != DR_VARIANT_TAG) {
+    if constexpr (!TR::TAG) {
         const S dx = st[F_POS + 0] - st[F_TGT + 0];
         const S dy = st[F_POS + 1] - st[F_TGT + 1];
         const S dz = st[F_POS + 2] - st[F_TGT + 2];
         const S d = m_sqrt((dx * dx + dy * dy) + dz * dz);
-        if constexpr (VAR == KVAR_WAYPOINT) {
+        if constexpr (TR::WAYPT) {
             // the gym's form on the handle's radius and bonus; the caller
             // advances the course where `reached`
             r = (S)0.01 * -d;
             *reached = d < (S)wp->radius;
             if (*reached) r += (S)wp->bonus;
-        } else if constexpr (VAR != DR_VARIANT_VECTORIZED) {
+        } else if constexpr (!TR::VEC) {
             r = (S)0.01 * -d;
             if (d < (S)0.05) r += (S)1;
         } else {
@@ -1000,6 +1041,119 @@ __device__ inline const T *at(const T *base, int64_t i) {
                                        (uint32_t)((uint32_t)i * (uint32_t)sizeof(T)));
 }
 
+// ---- a variant's side state ----
+// The words an env carries beside st[]: in registers over a step or a rollout
+// launch, in memory in the arrays at EnvView::mot (moving: also the centre, in
+// the target's arrays).  env_step_kernel and env_rollout_kernel declare one
+// Side and call these; what each does for a variant is written here, once.
+// SideNone is the variant with no such words (gym, vectorized, tag).  The
+// moving variant's centre, motion and target velocity, the smooth variant's
+// forces and the wind's mean and gust stay locals of the kernels: wrapped in
+// any form (member, reference, always_inline function) moving's instruction
+// streams changed, wind's rollout lost a wave of occupancy and smooth's
+// changed streams missed the speed check.
+template <typename S, int VAR>
+struct SideNone {
+    // issue the loads, where the kernel's load order has them
+    template <bool NTL>
+    __device__ void load(const EnvView<S> &, int64_t) {}
+    // values formed from the loaded words, once every load is issued
+    __device__ void derive() {}
+    // "has landed" constraints: of every word (ahead of the rollout's loop),
+    // or of those the step has not read before its first store
+    __device__ void pin() const {}
+    __device__ void pin_late() const {}
+    // the words a step changes, written every step or launch
+    __device__ void store(const EnvView<S> &, int64_t) const {}
+    // the words only a reset (or a reach) changes
+    __device__ void store_after_reset(const EnvView<S> &, int64_t) const {}
+    // the variant's part of the reset branch, after gym_reset_regs, for env
+    // `gid` starting episode `ep_new`
+    __device__ void reset(uint32_t, uint32_t, uint64_t, int32_t, const VarArgs<VAR> &, S[F_N]) {}
+    // the obs floats past the gym's 15, as make_obs takes them (EXT: has
+    // some), and bringing them up to date ahead of an obs
+    static constexpr bool EXT = false;
+    __device__ const float *ext() const { return nullptr; }
+    __device__ void ext_update() {}
+};
+template <typename S, int VAR>
+struct Side : SideNone<S, VAR> {};
+
+// rk4: the quaternion's fourth word (the first three sit in st[F_EUL ..]),
+// one array of S, and its f32 for the obs
+template <typename S>
+struct Side<S, DR_VARIANT_RK4> : SideNone<S, DR_VARIANT_RK4> {
+    S qd;
+    float qx[1];
+    template <bool NTL>
+    __device__ void load(const EnvView<S> &v, int64_t i) {
+        qd = ld_in<NTL>(at(reinterpret_cast<S *>(v.mot), i));
+    }
+    __device__ void pin() const { asm volatile("" ::"v"(qd)); }
+    __device__ void pin_late() const { pin(); }
+    __device__ void store(const EnvView<S> &v, int64_t i) const {
+        st_out(at(reinterpret_cast<S *>(v.mot), i), qd);
+    }
+    __device__ void reset(uint32_t, uint32_t, uint64_t, int32_t,
+                          const VarArgs<DR_VARIANT_RK4> &, S st[F_N]) {
+        rk4_reset_quat(st, qd);
+    }
+    static constexpr bool EXT = true;
+    __device__ const float *ext() const { return qx; }
+    __device__ void ext_update() { qx[0] = (float)qd; }
+};
+
+// waypoints: the index within the episode and the reach counter
+template <typename S>
+struct Side<S, KVAR_WAYPOINT> : SideNone<S, KVAR_WAYPOINT> {
+    int32_t j, q;
+    template <bool NTL>
+    __device__ void load(const EnvView<S> &v, int64_t i) {
+        int32_t *const p = reinterpret_cast<int32_t *>(v.mot);
+        j = *at(p, i);
+        q = *at(p + v.stride, i);
+    }
+    __device__ void pin() const { asm volatile("" ::"v"(j), "v"(q)); }
+    __device__ void pin_late() const { pin(); }
+    __device__ void store(const EnvView<S> &v, int64_t i) const {
+        int32_t *const p = reinterpret_cast<int32_t *>(v.mot);
+        st_out(at(p, i), j);
+        st_out(at(p + v.stride, i), q);
+    }
+    // a new course; q counts on
+    __device__ void reset(uint32_t, uint32_t, uint64_t, int32_t, const VarArgs<KVAR_WAYPOINT> &,
+                          S[F_N]) {
+        j = 0;
+    }
+};
+
+// airframe: the episode's six words and their two reciprocals; a reset is
+// the words' only writer
+template <typename S>
+struct Side<S, KVAR_AIRFRAME> : SideNone<S, KVAR_AIRFRAME> {
+    Airframe af;
+    template <bool NTL>
+    __device__ void load(const EnvView<S> &v, int64_t i) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) af.w[k] = *at(v.mot + k * v.stride, i);
+    }
+    __device__ void derive() { af.recip(); }
+    __device__ void pin() const {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) asm volatile("" ::"v"(af.w[k]));
+    }
+    __device__ void store_after_reset(const EnvView<S> &v, int64_t i) const {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) *at(v.mot + k * v.stride, i) = af.w[k];
+    }
+    // the new episode's airframe (Philox in host-uniform mode too)
+    __device__ void reset(uint32_t k0, uint32_t k1, uint64_t gid, int32_t ep_new,
+                          const VarArgs<KVAR_AIRFRAME> &va, S[F_N]) {
+        airframe_draw(k0, k1, gid, ep_new, va, af.w);
+        af.recip();
+    }
+};
+
 // HU: reset draws from the host-uniform ring (parity mode).  A template
 // parameter, not a runtime branch, so the Philox reset path holds no global
 // load: a load there would make the waitcnt pass drain every outstanding
@@ -1014,24 +1168,8 @@ template <typename S, int VAR, bool MON, int RPW, bool HU, bool NTL>
 __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
                                                              StepIO io, FieldPtrs<S> fp,
                                                              VarArgs<VAR> va) {
-    constexpr int OD = od_of<VAR>();
-    constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
-    // the gym's stored target and reset (the smooth variant is the gym env
-    // behind a motor lag; the tag variant carries the gym's target unread)
-    constexpr bool TAG = VAR == DR_VARIANT_TAG;
-    // (and the rk4 variant, the gym's task on another state and integrator)
-    constexpr bool RK4 = VAR == DR_VARIANT_RK4;
-    // (and the gym env with wind, the gym's step behind a disturbance)
-    constexpr bool WIND = VAR == KVAR_WIND;
-    // (and the gym env on a waypoint course: the gym's step, a target that
-    // moves on when it is reached)
-    constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
-    // (and the gym env on a randomised airframe: the gym's step on the
-    // episode's mass, inertia and motor gains)
-    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 ||
-                              WIND || WAYPT || AIRF;
-    constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
+    using T = Traits<VAR>;
+    constexpr int OD = T::OD;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     // Every kernel argument the state loads need is materialised here, in
     // ONE batch of scalar loads: the compiler otherwise issues them in three
@@ -1070,56 +1208,37 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
     for (int k = 0; k < F_EUL; ++k) st[k] = ld_in<NTL>(at(fp.p[k], i));
     S cen[3];
-    float mp[9], tvel[3];
-    float fm[4], dev_sq = 0.f;      // smooth: motor forces, |command - force|^2
+    float mp[9], tvel[3];           // moving: centre, motion, target velocity
+    float wm[3], wg[3];             // wind: the episode's mean wind, the gust
+    float fm[4];                    // smooth: the motor forces
+    Side<S, VAR> sd;                // the other variants' side words
+    float dev_sq = 0.f;             // smooth: |command - force|^2
     // tag: the partner's position / velocity, the obs past the first 12, the
     // role (env ids 2j pursue; i and env_id_offset + i have one parity)
     S pp[3], pv[3];
     float tx[7];
     const bool pursuer = (i & 1) == 0;
     const float sigma = pursuer ? 1.0f : -1.0f;
-    // rk4: the quaternion's fourth word (the first three sit in st[F_EUL ..])
-    // and its f32 for the obs
-    S qd = (S)0;
-    float qx[1] = {0.f};
-    S *const p_qd = reinterpret_cast<S *>(v.mot);
-    // the obs past the gym's 15
-    const float *const ext = TAG ? tx : (SMOOTH ? fm : (RK4 ? qx : tvel));
-    if constexpr (SMOOTH) {
+    sd.template load<NTL>(v, i);
+    if constexpr (T::SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
-    if constexpr (RK4) qd = ld_in<NTL>(at(p_qd, i));
-    // wind: the episode's mean wind and the gust
-    float wm[3], wg[3];
-    if constexpr (WIND) {
+    if constexpr (T::WIND) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             wm[k] = *at(v.mot + k * v.stride, i);
             wg[k] = *at(v.mot + (3 + k) * v.stride, i);
         }
     }
-    // waypoints: the index within the episode and the reach counter
-    int32_t wj = 0, wq = 0;
-    int32_t *const p_wp = reinterpret_cast<int32_t *>(v.mot);
-    if constexpr (WAYPT) {
-        wj = *at(p_wp, i);
-        wq = *at(p_wp + v.stride, i);
-    }
-    // airframe: the episode's six words
-    Airframe af;
-    if constexpr (AIRF) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) af.w[k] = *at(v.mot + k * v.stride, i);
-    }
-    if constexpr (TAG) {
+    if constexpr (T::TAG) {
         // nothing in the step reads the stored target: a reset writes it
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = (S)0;
-    } else if constexpr (GYMSTATE) {
+    } else if constexpr (T::GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = ld_in<NTL>(at(fp.p[k], i));
-    } else if constexpr (VAR == DR_VARIANT_MOVING) {
+    } else if constexpr (T::MOVING) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) cen[k] = *at(fp.p[F_TGT + k], i);
 #pragma unroll
@@ -1134,7 +1253,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // stall the wave on a dependent global load (+12 B per step, counted in
     // the measured traffic, not in the 305 B algorithmic)
     double eps_old = 0.0;
-    if constexpr (GYMLIKE) {
+    if constexpr (T::GYMLIKE) {
         ep_old = *at(p_epn, i);
         // eps loaded with the state: the Philox reset path holds no global
         // load (6-8 % faster at 65,536-131,072 envs than loading it in the reset)
@@ -1153,37 +1272,38 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // s_waitcnt holds back the issue of the remaining ones by a full memory
     // latency.
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (VAR == DR_VARIANT_MOVING) {
+    sd.derive();
+    if constexpr (T::MOVING) {
         // the reward and obs of this step see the target at the NEW step
         moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
     }
 
     // the gust and the drag impulse sit in front of the gym step, on the
     // step counter and episode the step starts from
-    if constexpr (WIND)
+    if constexpr (T::WIND)
         wind_pre<S>(st, wm, wg, va, v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old,
                     step, v.dt);
     bool crash;
     bool reached = false;
     S r;
-    if constexpr (SMOOTH) {
+    if constexpr (T::SMOOTH) {
         // the physics sees the lagged forces, not the command
         r = physics_step<S, VAR>(st, smooth_filter(act, fm, va.alpha, dev_sq), v.dt, crash);
-    } else if constexpr (RK4) {
-        r = rk4_step<S>(st, qd, motor_mix(act), v.dt, rk4_h6<S>(va), crash);
-    } else if constexpr (WAYPT) {
+    } else if constexpr (T::RK4) {
+        r = rk4_step<S>(st, sd.qd, motor_mix(act), v.dt, rk4_h6<S>(va), crash);
+    } else if constexpr (T::WAYPT) {
         r = physics_step<S, VAR>(st, act, v.dt, crash, &va, &reached);
-    } else if constexpr (AIRF) {
+    } else if constexpr (T::AIRF) {
         // the motor mixes of the gained command, the physics on 1/m and 1/s
-        af.recip();
-        r = physics_step<S, VAR>(st, airframe_gain(af, act), v.dt, crash, nullptr, nullptr, &af);
+        r = physics_step<S, VAR>(st, airframe_gain(sd.af, act), v.dt, crash, nullptr, nullptr,
+                                 &sd.af);
     } else {
         r = physics_step<S, VAR>(st, act, v.dt, crash);
     }
     DR_STAMP(2);
     step += 1;                                             // (155)
     bool done, any_crash = crash;   // any_crash: own or (tag) the partner's
-    if constexpr (TAG) {
+    if constexpr (T::TAG) {
         // Wave-uniform code (dead lanes ran the physics on row n - 1, and
         // their partners are dead too): exchange the new position and
         // velocity and the own crash / done flags, then the pair's reward
@@ -1198,12 +1318,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         done = live && (crash || (step >= v.max_steps));   // (156-157)
     }
     float rf = (float)r;                                   // SB3 f32 buffer
-    if constexpr (SMOOTH) {
+    if constexpr (T::SMOOTH) {
         // uniform branch: at lam == 0 the reward is the gym's even where
         // dev_sq overflowed
         if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
     }
-    if constexpr (TAG) {
+    if constexpr (T::TAG) {
         // uniform branch, one f32 subtract for the lanes that crashed
         if (va.crash != 0.f) rf = crash ? rf - va.crash : rf;
     }
@@ -1217,21 +1337,20 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     // in the reset branch and again where it rejoins, for every wave.
     asm volatile("" ::"v"(step), "v"(ep_old), "v"(eps_old), "v"(ret0), "v"(len0));
 #pragma unroll
-    for (int k = 0; k < (TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
-    if constexpr (RK4) asm volatile("" ::"v"(qd));
-    if constexpr (WAYPT) asm volatile("" ::"v"(wj), "v"(wq));
+    for (int k = 0; k < (T::TAG ? 12 : F_N); ++k) asm volatile("" ::"v"(st[k]));
+    sd.pin_late();
     if (live) {
         st_out(at(io.rew, i), rf);
         st_out(at(io.done, i), (uint8_t)done);
     }
-    if constexpr (WAYPT) {
+    if constexpr (T::WAYPT) {
         // the course moves on, ahead of the terminal obs and of a reset
         // (which overwrites the target it stores)
         if (reached && live) {
-            wj += 1;
-            wq += 1;
+            sd.j += 1;
+            sd.q += 1;
             waypoint_draw<S>(st, v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old,
-                             eps_old, wj);
+                             eps_old, sd.j);
 #pragma unroll
             for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
         }
@@ -1243,22 +1362,23 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
         ret = ret0 + rf;                                   // VecMonitor
         len = len0 + 1;
     }
-    if constexpr (GYMLIKE) {
+    if constexpr (T::GYMLIKE) {
         if (done && io.auto_reset) {
             // DummyVecEnv: keep the terminal obs, reset in the same step.
             if (io.term_obs) {
                 // tag: the partner's terminal state, exchanged before the branch
-                if constexpr (TAG) tag_ext(st, pp, pv, sigma, tx);
-                if constexpr (RK4) qx[0] = (float)qd;
-                make_obs<S, VAR>(st, ob, ext);
+                if constexpr (T::TAG) tag_ext(st, pp, pv, sigma, tx);
+                sd.ext_update();
+                make_obs<S, VAR>(st, ob, T::TAG ? tx : (T::MOVING ? tvel : (T::SMOOTH ? fm : sd.ext())));
 #pragma unroll
                 for (int k = 0; k < OD; ++k) io.term_obs[i * OD + k] = ob[k];
             }
             step = 0;
-            if constexpr (GYMSTATE) {
+            if constexpr (T::GYMSTATE) {
                 gym_reset_regs(v, i, HU ? 1 : 0, st, ep_old, eps_old);
-                if constexpr (RK4) rk4_reset_quat(st, qd);
-                if constexpr (WIND) {
+                sd.reset(v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old + 1, va, st);
+                sd.store_after_reset(v, i);
+                if constexpr (T::WIND) {
                     // the new episode's mean wind (Philox in host-uniform
                     // mode too), still air around it
                     wind_mean(v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i), ep_old + 1,
@@ -1266,18 +1386,9 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
                     for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                 }
-                if constexpr (WAYPT) wj = 0;   // a new course; q counts on
-                if constexpr (AIRF) {
-                    // the new episode's airframe (Philox in host-uniform mode
-                    // too); a reset is the six words' only writer
-                    airframe_draw(v.seed_lo, v.seed_hi, (uint64_t)(v.env_id_offset + i),
-                                  ep_old + 1, va, af.w);
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) *at(v.mot + k * v.stride, i) = af.w[k];
-                }
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
-                if constexpr (SMOOTH) {
+                if constexpr (T::SMOOTH) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) fm[k] = kHover32;
                 }
@@ -1291,7 +1402,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
             }
         }
     }
-    if constexpr (TAG) {
+    if constexpr (T::TAG) {
         // The reset branch has rejoined: the partner's state once more, now
         // post-reset (both members of a pair reset in the same step).  Skipped,
         // wave-uniformly, when no lane reset: the values are those of the
@@ -1301,8 +1412,8 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
     }
     // ONE observation pass over the post-reset state (the terminal obs is
     // formed inside the reset branch only when the caller keeps it)
-    if constexpr (RK4) qx[0] = (float)qd;
-    make_obs<S, VAR>(st, ob, ext);
+    sd.ext_update();
+    make_obs<S, VAR>(st, ob, T::TAG ? tx : (T::MOVING ? tvel : (T::SMOOTH ? fm : sd.ext())));
     if constexpr (MON) {
         if (io.trunc_out && live) *at(io.trunc_out, i) = (uint8_t)(done && !any_crash);
         if (done) {               // VecMonitor: report, then restart counters
@@ -1321,21 +1432,17 @@ __global__ __launch_bounds__(kEnvBlock) void env_step_kernel(EnvView<S> v,
 #pragma unroll
         for (int k = 0; k < 12; ++k) st_out(at(fp.p[k], i), st[k]);
         st_out(at(p_step, i), step);
-        if constexpr (SMOOTH) {
+        sd.store(v, i);
+        if constexpr (T::SMOOTH) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
-        if constexpr (RK4) st_out(at(p_qd, i), qd);
-        if constexpr (WIND) {
+        if constexpr (T::WIND) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 st_out(at(v.mot + k * v.stride, i), wm[k]);
                 st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
             }
-        }
-        if constexpr (WAYPT) {
-            st_out(at(p_wp, i), wj);
-            st_out(at(p_wp + v.stride, i), wq);
         }
     }
     DR_STAMP(4);
@@ -1398,20 +1505,8 @@ template <typename S, int VAR, int RPW, bool GEN>
 __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, RolloutIO io,
                                                                 FieldPtrs<S> fp,
                                                                 VarArgs<VAR> va) {
-    constexpr int OD = od_of<VAR>();
-    constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
-    constexpr bool TAG = VAR == DR_VARIANT_TAG;
-    constexpr bool RK4 = VAR == DR_VARIANT_RK4;
-    constexpr bool WIND = VAR == KVAR_WIND;
-    // (and the gym env on a waypoint course: the gym's step, a target that
-    // moves on when it is reached)
-    constexpr bool WAYPT = VAR == KVAR_WAYPOINT;
-    // (and the gym env on a randomised airframe: the gym's step on the
-    // episode's mass, inertia and motor gains)
-    constexpr bool AIRF = VAR == KVAR_AIRFRAME;
-    constexpr bool GYMSTATE = VAR == DR_VARIANT_GYM || VAR == DR_VARIANT_SMOOTH || TAG || RK4 ||
-                              WIND || WAYPT || AIRF;
-    constexpr bool SMOOTH = VAR == DR_VARIANT_SMOOTH;
+    using T = Traits<VAR>;
+    constexpr int OD = T::OD;
     __shared__ float4 sh4[kEnvBlock * OD / 4];
     const int64_t n_ = v.n;
     const int64_t base = (int64_t)blockIdx.x * (kEnvWpb * RPW);
@@ -1427,53 +1522,36 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     for (int k = 0; k < F_EUL; ++k) st[k] = *at(fp.p[k], i);
     S cen[3];
     float mp[9], tvel[3];
-    // smooth: the motor forces, carried in registers over the launch, and
-    // this step's |command - force|^2
-    float fm[4], dev_sq = 0.f;
+    // the variant's side words, carried in registers over the launch like
+    // the rest of the state (airframe: with the two reciprocals)
+    Side<S, VAR> sd;
+    float wm[3], wg[3];    // wind: the mean wind and the gust, likewise
+    float fm[4];           // smooth: the motor forces, likewise
+    float dev_sq = 0.f;    // smooth: this step's |command - force|^2
     // tag: the obs past the first 12 and the role (env_step_kernel)
     float tx[7];
     const bool pursuer = (i & 1) == 0;
     const float sigma = pursuer ? 1.0f : -1.0f;
-    // rk4: the quaternion's fourth word, carried in a register over the
-    // launch like the rest of the state, and its f32 for the obs
-    S qd = (S)0;
-    float qx[1] = {0.f};
-    S *const p_qd = reinterpret_cast<S *>(v.mot);
-    const float *const ext = TAG ? tx : (SMOOTH ? fm : (RK4 ? qx : tvel));
-    if constexpr (SMOOTH) {
+    // the obs past the gym's 15 (tvel: the moving variant's; unread elsewhere)
+    const float *const ext =
+        T::TAG ? tx : (T::SMOOTH ? fm : (Side<S, VAR>::EXT ? sd.ext() : tvel));
+    sd.template load<false>(v, i);
+    sd.derive();
+    if constexpr (T::SMOOTH) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fm[k] = *at(v.mot + k * v.stride, i);
     }
-    if constexpr (RK4) qd = *at(p_qd, i);
-    // wind: the mean wind and the gust, carried in registers over the launch
-    float wm[3], wg[3];
-    if constexpr (WIND) {
+    if constexpr (T::WIND) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             wm[k] = *at(v.mot + k * v.stride, i);
             wg[k] = *at(v.mot + (3 + k) * v.stride, i);
         }
     }
-    // waypoints: the index and the reach counter, carried in registers over
-    // the launch, as is the current waypoint (the target)
-    int32_t wj = 0, wq = 0;
-    int32_t *const p_wp = reinterpret_cast<int32_t *>(v.mot);
-    if constexpr (WAYPT) {
-        wj = *at(p_wp, i);
-        wq = *at(p_wp + v.stride, i);
-    }
-    // airframe: the six words and the two reciprocals, carried in registers
-    // over the launch; a reset redraws them
-    Airframe af;
-    if constexpr (AIRF) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) af.w[k] = *at(v.mot + k * v.stride, i);
-        af.recip();
-    }
-    if constexpr (GYMSTATE) {
+    if constexpr (T::GYMSTATE) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
-    } else if constexpr (VAR == DR_VARIANT_MOVING) {
+    } else if constexpr (T::MOVING) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) cen[k] = *at(fp.p[F_TGT + k], i);
 #pragma unroll
@@ -1486,7 +1564,7 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     int32_t step = *at(fp.step, i);
     int32_t ep_num = 0;
     double eps = 0.0;
-    if constexpr (GYMLIKE) {
+    if constexpr (T::GYMLIKE) {
         ep_num = *at(fp.ep_num, i);
         eps = *at(fp.eps, i);
     }
@@ -1506,13 +1584,13 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     // waves hold a resetting env at each step under the random policy).  A
     // lane resetting twice within one group draws in the branch as before;
     // the draws are the same Philox words either way.
-    constexpr int NB = VAR == DR_VARIANT_MOVING ? 4 : 1;   // Philox blocks per reset
+    constexpr int NB = T::NB;
     u32x4 nd[NB] = {};
     bool nd_ok = false;
-    // (airframe: the next episode's six words and two reciprocals ride with
-    // them, so the branch holds neither their two Philox blocks nor the two
-    // divides; the values are the same either way)
-    Airframe afn;
+    // (Traits::SIDE_AHEAD, the airframe: the next episode's six words and two
+    // reciprocals ride with them, so the branch holds neither their two Philox
+    // blocks nor the two divides; the values are the same either way)
+    Side<S, VAR> sdn;
     // the step limit in a VGPR: under the kernel's SGPR pressure the
     // compiler otherwise re-reads it from the kernel arguments at every
     // step (a scalar load and its wait on the critical path)
@@ -1523,43 +1601,41 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
     // the motor mixes the physics sees for command `act`: the command's own,
     // or (smooth) those of the lagged forces, which the lag updates here
     auto mix_of = [&](const float4 act) -> MotorMix {
-        if constexpr (SMOOTH) return motor_mix(smooth_filter(act, fm, va.alpha, dev_sq));
-        else if constexpr (AIRF) return motor_mix(airframe_gain(af, act));
+        if constexpr (T::SMOOTH) return motor_mix(smooth_filter(act, fm, va.alpha, dev_sq));
+        else if constexpr (T::AIRF) return motor_mix(airframe_gain(sd.af, act));
         else return motor_mix(act);
     };
     auto step_one = [&](const MotorMix mx, const int t) {
         asm volatile("" : "+s"(vk.seed_lo), "+s"(vk.seed_hi));
-        if constexpr (GYMLIKE) {
+        if constexpr (T::GYMLIKE) {
             if (t % kResetAhead == 0 && !nd_ok) {
 #pragma unroll
                 for (int b = 0; b < NB; ++b)
                     nd[b] = philox4x32_10(u32x4{(uint32_t)(ep_num + 1), (uint32_t)gid,
                                                 (uint32_t)(gid >> 32), TAG_RESET | (uint32_t)b},
                                           vk.seed_lo, vk.seed_hi);
-                if constexpr (AIRF) {
-                    airframe_draw(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, afn.w);
-                    afn.recip();
-                }
+                if constexpr (T::SIDE_AHEAD)
+                    sdn.reset(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, st);
                 nd_ok = true;
             }
         }
-        if constexpr (VAR == DR_VARIANT_MOVING)
+        if constexpr (T::MOVING)
             moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
-        if constexpr (WIND)
+        if constexpr (T::WIND)
             wind_pre<S>(st, wm, wg, va, vk.seed_lo, vk.seed_hi, gid, ep_num, step, v.dt);
         bool crash;
         bool reached = false;
         S r;
-        if constexpr (RK4) r = rk4_step<S>(st, qd, mx, v.dt, rk4_h6<S>(va), crash);
-        else if constexpr (WAYPT)
+        if constexpr (T::RK4) r = rk4_step<S>(st, sd.qd, mx, v.dt, rk4_h6<S>(va), crash);
+        else if constexpr (T::WAYPT)
             r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, &va, &reached);
-        else if constexpr (AIRF)
-            r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, nullptr, nullptr, &af);
+        else if constexpr (T::AIRF)
+            r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash, nullptr, nullptr, &sd.af);
         else r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
         bool done;
         S pp[3], pv[3];
-        if constexpr (TAG) {
+        if constexpr (T::TAG) {
             // wave-uniform: the exchanges of env_step_kernel, all in registers
             // (no global store is added to the step)
             const int own = (int)crash | ((int)(crash || (step >= max_steps)) << 1);
@@ -1572,11 +1648,11 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         }
         const int64_t row = (int64_t)t * n_;
         if (live) {
-            if constexpr (TAG) {
+            if constexpr (T::TAG) {
                 float rf = (float)r;
                 if (va.crash != 0.f) rf = crash ? rf - va.crash : rf;
                 st_out(at(io.rew + row, i), rf);
-            } else if constexpr (SMOOTH) {
+            } else if constexpr (T::SMOOTH) {
                 float rf = (float)r;
                 // uniform branch, as in env_step_kernel
                 if (va.lam != 0.f) rf = rf - va.lam * dev_sq;
@@ -1586,42 +1662,38 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
             }
             st_out(at(io.done + row, i), (uint8_t)done);
         }
-        if constexpr (WAYPT) {
+        if constexpr (T::WAYPT) {
             // the course moves on (env_step_kernel), all in registers; the
             // target is written back at the end, as after a reset
             if (reached && live) {
-                wj += 1;
-                wq += 1;
-                waypoint_draw<S>(st, vk.seed_lo, vk.seed_hi, gid, ep_num, eps, wj);
+                sd.j += 1;
+                sd.q += 1;
+                waypoint_draw<S>(st, vk.seed_lo, vk.seed_hi, gid, ep_num, eps, sd.j);
                 reset_any = true;
             }
         }
-        if constexpr (GYMLIKE) {
+        if constexpr (T::GYMLIKE) {
             if (done && io.auto_reset) {
                 step = 0;
                 reset_any = true;
-                if constexpr (GYMSTATE) {
-                    if constexpr (AIRF) {
-                        if (nd_ok) {
-                            af = afn;
-                        } else {
-                            airframe_draw(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, af.w);
-                            af.recip();
-                        }
+                if constexpr (T::GYMSTATE) {
+                    if constexpr (T::SIDE_AHEAD) {
+                        if (nd_ok) sd = sdn;
+                        else sd.reset(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, st);
                     }
                     gym_reset_regs(vk, i, 0, st, ep_num, eps, nd_ok ? &nd[0] : nullptr);
                     nd_ok = false;
-                    if constexpr (RK4) rk4_reset_quat(st, qd);
-                    if constexpr (SMOOTH) {
+                    if constexpr (T::SIDE && !T::SIDE_AHEAD)
+                        sd.reset(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va, st);
+                    if constexpr (T::SMOOTH) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) fm[k] = kHover32;
                     }
-                    if constexpr (WIND) {
+                    if constexpr (T::WIND) {
                         wind_mean(vk.seed_lo, vk.seed_hi, gid, ep_num + 1, va.W, wm);
 #pragma unroll
                         for (int k = 0; k < 3; ++k) wg[k] = 0.f;
                     }
-                    if constexpr (WAYPT) wj = 0;
                 } else {
                     moving_reset_regs(vk, i, 0, st, cen, mp, ep_num, eps, nd_ok ? nd : nullptr);
                     nd_ok = false;
@@ -1633,12 +1705,12 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
                 if (ep_num % 2000 == 0) eps += 0.1;
             }
         }
-        if constexpr (TAG) {
+        if constexpr (T::TAG) {
             // rejoined: the partner's post-reset state (env_step_kernel)
             if (__any(done && io.auto_reset)) tag_partner(st, pp, pv);
             tag_ext(st, pp, pv, sigma, tx);
         }
-        if constexpr (RK4) qx[0] = (float)qd;
+        if constexpr (Side<S, VAR>::EXT) sd.ext_update();
         make_obs<S, VAR>(st, ob, ext);
         if (!live) {
 #pragma unroll
@@ -1682,25 +1754,20 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
         asm volatile("" ::"v"(ep_num), "v"(eps), "v"(a), "v"(b), "v"(step));
 #pragma unroll
         for (int k = 0; k < F_N; ++k) asm volatile("" ::"v"(st[k]));
-        if constexpr (RK4) asm volatile("" ::"v"(qd));
-        if constexpr (VAR == DR_VARIANT_MOVING) {
+        sd.pin();
+        if constexpr (T::SMOOTH) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(fm[k]));
+        }
+        if constexpr (T::WIND) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(wm[k]), "v"(wg[k]));
+        }
+        if constexpr (T::MOVING) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(cen[k]));
 #pragma unroll
             for (int k = 0; k < 9; ++k) asm volatile("" ::"v"(mp[k]));
-        }
-        if constexpr (SMOOTH) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(fm[k]));
-        }
-        if constexpr (WIND) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) asm volatile("" ::"v"(wm[k]), "v"(wg[k]));
-        }
-        if constexpr (WAYPT) asm volatile("" ::"v"(wj), "v"(wq));
-        if constexpr (AIRF) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) asm volatile("" ::"v"(af.w[k]));
         }
         // Two steps ahead, in two registers that alternate (the loop is
         // unrolled by two so each keeps its role): step t's action was
@@ -1739,32 +1806,25 @@ __global__ __launch_bounds__(kEnvBlock) void env_rollout_kernel(EnvView<S> v, Ro
 #pragma unroll
         for (int k = 0; k < 12; ++k) st_out(at(fp.p[k], i), st[k]);
         st_out(at(fp.step, i), step);
-        if constexpr (SMOOTH) {
+        sd.store(v, i);
+        if constexpr (T::SMOOTH) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) st_out(at(v.mot + k * v.stride, i), fm[k]);
         }
-        if constexpr (RK4) st_out(at(p_qd, i), qd);
-        if constexpr (WIND) {
+        if constexpr (T::WIND) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 st_out(at(v.mot + k * v.stride, i), wm[k]);
                 st_out(at(v.mot + (3 + k) * v.stride, i), wg[k]);
             }
         }
-        if constexpr (WAYPT) {
-            st_out(at(p_wp, i), wj);
-            st_out(at(p_wp + v.stride, i), wq);
-        }
         // (waypoints: or reached a waypoint, which moves the target too)
         if (reset_any) {
-            if constexpr (GYMSTATE) {
+            if constexpr (T::GYMSTATE) {
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
-                if constexpr (AIRF) {
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) *at(v.mot + k * v.stride, i) = af.w[k];
-                }
-            } else if constexpr (VAR == DR_VARIANT_MOVING) {
+                sd.store_after_reset(v, i);
+            } else if constexpr (T::MOVING) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) *at(fp.p[F_TGT + k], i) = cen[k];
 #pragma unroll
@@ -1838,8 +1898,8 @@ struct WsLds {
 template <typename S, int VAR, bool GEN>
 __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v, RolloutIO io,
                                                                     FieldPtrs<S> fp) {
-    constexpr int OD = od_of<VAR>();
-    constexpr bool GYMLIKE = VAR != DR_VARIANT_VECTORIZED;
+    using T = Traits<VAR>;
+    constexpr int OD = T::OD;
     constexpr int NQ = (64 * OD / 4 + 63) / 64;  // float4 rows-stores per lane and step
     // the hand-counted wait assumes NQ obs + 1 reward + 1 done store per phase
     constexpr int S_OPS = NQ + 2;
@@ -1950,7 +2010,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
     if constexpr (VAR == DR_VARIANT_GYM) {
 #pragma unroll
         for (int k = F_TGT; k < F_N; ++k) st[k] = *at(fp.p[k], i);
-    } else if constexpr (VAR == DR_VARIANT_MOVING) {
+    } else if constexpr (T::MOVING) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) cen[k] = *at(fp.p[F_TGT + k], i);
 #pragma unroll
@@ -1963,7 +2023,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
     int32_t step = *at(fp.step, i);
     int32_t ep_num = 0;
     double eps = 0.0;
-    if constexpr (GYMLIKE) {
+    if constexpr (T::GYMLIKE) {
         ep_num = *at(fp.ep_num, i);
         eps = *at(fp.eps, i);
     }
@@ -1975,7 +2035,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
     EnvView<S> vk = v;
     // the next reset's Philox blocks drawn ahead, once per group of
     // kResetAhead steps (env_rollout_kernel)
-    constexpr int NB = VAR == DR_VARIANT_MOVING ? 4 : 1;
+    constexpr int NB = T::NB;
     u32x4 nd[NB] = {};
     bool nd_ok = false;
     int32_t max_steps;
@@ -1985,7 +2045,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
         asm volatile("" : "+s"(vk.seed_lo), "+s"(vk.seed_hi));
         const float4 a_cur = sh.act[t % kWsNA][p * 64 + lane];
         const MotorMix mx = motor_mix(a_cur);
-        if constexpr (GYMLIKE) {
+        if constexpr (T::GYMLIKE) {
             if (t % kResetAhead == 0 && !nd_ok) {
 #pragma unroll
                 for (int b = 0; b < NB; ++b)
@@ -1995,14 +2055,14 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
                 nd_ok = true;
             }
         }
-        if constexpr (VAR == DR_VARIANT_MOVING)
+        if constexpr (T::MOVING)
             moving_target(cen, mp, step + 1, (float)v.dt, &st[F_TGT], tvel);
         bool crash;
         S r;
         r = physics_step_mixed<S, VAR>(st, mx, v.dt, crash);
         step += 1;
         const bool done = live && (crash || (step >= max_steps));
-        if constexpr (GYMLIKE) {
+        if constexpr (T::GYMLIKE) {
             const bool rs = done && io.auto_reset;
             if (rs) {
                 step = 0;
@@ -2052,7 +2112,7 @@ __global__ __launch_bounds__(kWsThreads) void env_rollout_ws_kernel(EnvView<S> v
             if constexpr (VAR == DR_VARIANT_GYM) {
 #pragma unroll
                 for (int k = F_TGT; k < F_N; ++k) *at(fp.p[k], i) = st[k];
-            } else if constexpr (VAR == DR_VARIANT_MOVING) {
+            } else if constexpr (T::MOVING) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) *at(fp.p[F_TGT + k], i) = cen[k];
 #pragma unroll
@@ -2114,7 +2174,7 @@ struct AbLds {
 template <typename S>
 __global__ __launch_bounds__(kAbThreads) void env_rollout_ab_kernel(EnvView<S> v, RolloutIO io,
                                                                     FieldPtrs<S> fp) {
-    constexpr int OD = od_of<DR_VARIANT_GYM>();
+    constexpr int OD = Traits<DR_VARIANT_GYM>::OD;
     constexpr int NQ = (64 * OD / 4 + 63) / 64;
     constexpr int S_OPS = NQ + 2;
     static_assert(S_OPS + kWsAhead * (S_OPS + 1) <= 63, "the action-load wait count must fit vmcnt");
@@ -2427,7 +2487,7 @@ __global__ __launch_bounds__(kBlock) void env_reset_kernel(EnvView<S> v,
                                                            const uint8_t *mask,
                                                            float *obs, int mode,
                                                            int init) {
-    constexpr int OD = od_of<VAR>();
+    constexpr int OD = Traits<VAR>::OD;
     __shared__ float4 sh4[kBlock * OD / 4];
     const int64_t base = (int64_t)blockIdx.x * kBlock;
     const int64_t i = base + threadIdx.x;
@@ -2750,25 +2810,21 @@ struct dr_handle {
     // DR_VARIANT_TAG (dr_set_tag): passed to each launch
     float tag_radius = 0.25f;
     float crash_penalty = 0.0f;
-    // DR_VARIANT_GYM (dr_set_wind): the parameters as given, the two the host
-    // derives from them (b = 1 - gust_rate, c = sigma sqrt(3 (1 - b^2))), and
-    // the six f32 arrays of `stride` elements the first non-neutral call
-    // allocates; while null the handle launches the gym's kernels
+    // DR_VARIANT_GYM, its options (dr_set_wind, dr_set_waypoints,
+    // dr_set_airframe).  At most one is enabled: `opt_kind` says which, and
+    // `opt` is its allocation of `stride`-element arrays (wind: 6 f32, mean
+    // and gust; waypoints: 2 i32, j and q; airframe: 6 f32, m, s, g0..g3),
+    // made by the first enabling call; while OPT_NONE the handle launches the
+    // gym's kernels.  The parameters are kept as given and passed to each
+    // launch; gust_b = 1 - gust_rate and gust_c = sigma sqrt(3 (1 - b^2)) are
+    // the two the host derives.
+    enum Opt : int { OPT_NONE = 0, OPT_WIND, OPT_WAYPOINT, OPT_AIRFRAME };
+    int opt_kind = OPT_NONE;
+    void *opt = nullptr;
     float drag = 0.0f, wind_speed = 0.0f, gust_sigma = 0.0f, gust_rate = 0.0f;
     float gust_b = 1.0f, gust_c = 0.0f;
-    float *wind = nullptr;
-    // DR_VARIANT_GYM (dr_set_waypoints): the reach radius and bonus, passed to
-    // each launch, and the two i32 arrays of `stride` elements (j, q) the
-    // first call allocates; while null the handle launches the gym's kernels.
-    // At most one of `wind` and `wp` is set.
     float reach_radius = 0.0f, reach_bonus = 0.0f;
-    int32_t *wp = nullptr;
-    // DR_VARIANT_GYM (dr_set_airframe): the three spreads, passed to each
-    // launch, and the six f32 arrays of `stride` elements (m, s, g0..g3) the
-    // first non-neutral call allocates; while null the handle launches the
-    // gym's kernels.  At most one of `wind`, `wp` and `air` is set.
     float mass_spread = 0.0f, inertia_spread = 0.0f, motor_spread = 0.0f;
-    float *air = nullptr;
     void *mem = nullptr;
     const double *host_u = nullptr;
     std::string err;
@@ -2790,6 +2846,38 @@ int fail(dr_handle *h, int code, const std::string &msg) {
     return code;
 }
 
+// The epilogue of every kernel launch: `what` prefixes the HIP error's text.
+int launched(dr_handle *h, const std::string &what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, DR_ERR_HIP, what + ": " + hipGetErrorString(e));
+    return DR_OK;
+}
+
+// f(std::integral_constant<int, V>{}) for a variant id (a public dr_variant or
+// one of this file's KVAR_ tags) as a compile-time value: the one list of
+// variant ids on the host; what differs between them comes from Traits<V>.
+template <typename F>
+auto for_variant(int variant, F &&f) {
+    switch (variant) {
+        case DR_VARIANT_GYM: return f(std::integral_constant<int, DR_VARIANT_GYM>{});
+        case KVAR_WIND: return f(std::integral_constant<int, KVAR_WIND>{});
+        case KVAR_WAYPOINT: return f(std::integral_constant<int, KVAR_WAYPOINT>{});
+        case KVAR_AIRFRAME: return f(std::integral_constant<int, KVAR_AIRFRAME>{});
+        case DR_VARIANT_MOVING: return f(std::integral_constant<int, DR_VARIANT_MOVING>{});
+        case DR_VARIANT_SMOOTH: return f(std::integral_constant<int, DR_VARIANT_SMOOTH>{});
+        case DR_VARIANT_TAG: return f(std::integral_constant<int, DR_VARIANT_TAG>{});
+        case DR_VARIANT_RK4: return f(std::integral_constant<int, DR_VARIANT_RK4>{});
+        default: return f(std::integral_constant<int, DR_VARIANT_VECTORIZED>{});
+    }
+}
+// bytes per env behind the monitor counters
+template <typename S>
+size_t mot_bytes(int variant) {
+    return for_variant(variant, [](auto var) {
+        return Traits<decltype(var)::value>::template mot_bytes<S>();
+    });
+}
+
 template <typename S>
 EnvView<S> view_of(const dr_handle *h) {
     EnvView<S> v{};
@@ -2802,14 +2890,10 @@ EnvView<S> view_of(const dr_handle *h) {
     v.ep_num = reinterpret_cast<int32_t *>(m + Layout<S>::ep_num(sp));
     v.ep_ret = reinterpret_cast<float *>(m + Layout<S>::ep_ret(sp));
     v.ep_len = reinterpret_cast<int32_t *>(m + Layout<S>::ep_len(sp));
-    // (rk4: one array of S there, the quaternion's fourth word)
-    v.mot = (h->cfg.variant == DR_VARIANT_MOVING || h->cfg.variant == DR_VARIANT_SMOOTH ||
-             h->cfg.variant == DR_VARIANT_RK4)
-                ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
-                : (h->cfg.variant == DR_VARIANT_GYM
-                       ? (h->wp ? reinterpret_cast<float *>(h->wp)
-                                : (h->air ? h->air : h->wind))
-                       : nullptr);
+    // the variant's own arrays behind the counters, else (gym) the enabled
+    // option's allocation, else null
+    v.mot = mot_bytes<S>(h->cfg.variant) ? reinterpret_cast<float *>(m + Layout<S>::mot(sp))
+                                         : static_cast<float *>(h->opt);
     v.n = h->n;
     v.env_id_offset = h->cfg.env_id_offset;
     v.host_u = h->host_u;
@@ -2821,12 +2905,9 @@ EnvView<S> view_of(const dr_handle *h) {
 }
 
 size_t state_bytes(int64_t stride, int dtype, int variant) {
-    const size_t s = dtype == DR_STATE_F64 ? sizeof(double) : sizeof(float);
-    const size_t mot = variant == DR_VARIANT_MOVING
-                           ? 9 * sizeof(float)
-                           : (variant == DR_VARIANT_SMOOTH
-                                  ? 4 * sizeof(float)
-                                  : (variant == DR_VARIANT_RK4 ? s : 0));
+    const bool f64 = dtype == DR_STATE_F64;
+    const size_t s = f64 ? sizeof(double) : sizeof(float);
+    const size_t mot = f64 ? mot_bytes<double>(variant) : mot_bytes<float>(variant);
     return (size_t)F_N * stride * s + (size_t)stride * (8 + 4 + 4 + 4 + 4 + mot);
 }
 
@@ -2850,23 +2931,10 @@ struct TypeTag {
 };
 template <typename F>
 int with_state(const dr_handle *h, F &&f) {
-    auto by_variant = [&](auto s) {
-        switch (h->cfg.variant) {
-            case DR_VARIANT_GYM:
-                // with wind enabled: the gym-with-wind kernels
-                if (h->wind) return f(s, std::integral_constant<int, KVAR_WIND>{});
-                // on a waypoint course: the gym-with-waypoints kernels
-                if (h->wp) return f(s, std::integral_constant<int, KVAR_WAYPOINT>{});
-                // on randomised airframes: the gym-with-airframe kernels
-                if (h->air) return f(s, std::integral_constant<int, KVAR_AIRFRAME>{});
-                return f(s, std::integral_constant<int, DR_VARIANT_GYM>{});
-            case DR_VARIANT_MOVING: return f(s, std::integral_constant<int, DR_VARIANT_MOVING>{});
-            case DR_VARIANT_SMOOTH: return f(s, std::integral_constant<int, DR_VARIANT_SMOOTH>{});
-            case DR_VARIANT_TAG: return f(s, std::integral_constant<int, DR_VARIANT_TAG>{});
-            case DR_VARIANT_RK4: return f(s, std::integral_constant<int, DR_VARIANT_RK4>{});
-            default: return f(s, std::integral_constant<int, DR_VARIANT_VECTORIZED>{});
-        }
-    };
+    // a gym handle with an option enabled launches that option's kernels
+    static constexpr int kOptVar[] = {DR_VARIANT_GYM, KVAR_WIND, KVAR_WAYPOINT, KVAR_AIRFRAME};
+    const int kv = h->cfg.variant == DR_VARIANT_GYM ? kOptVar[h->opt_kind] : h->cfg.variant;
+    auto by_variant = [&](auto s) { return for_variant(kv, [&](auto var) { return f(s, var); }); };
     return h->cfg.state_dtype == DR_STATE_F64 ? by_variant(TypeTag<double>{})
                                               : by_variant(TypeTag<float>{});
 }
@@ -2893,71 +2961,45 @@ int launch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
     EnvView<S> v = view_of<S>(h);
     hipLaunchKernelGGL((env_reset_kernel<S, VAR>), dim3(grid_for(h->n)),
                        dim3(kBlock), 0, st, v, mask, obs, mode, init);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("env_reset_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "env_reset_kernel");
 }
 
-// The mean wind of every env's (mask: the masked envs') current episode and a
-// zero gust, enqueued on `st`.
-int launch_wind_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
+// The enabled option's words for every env's (mask: the masked envs')
+// current episode, enqueued on `st` behind the gym's reset: the mean wind and
+// a zero gust; a new course (j = 0); the episode's airframe.
+int launch_option_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
     const int32_t *ep_num = h->cfg.state_dtype == DR_STATE_F64 ? view_of<double>(h).ep_num
                                                                : view_of<float>(h).ep_num;
-    hipLaunchKernelGGL(wind_fill_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->wind,
-                       h->stride, h->n, ep_num, h->cfg.env_id_offset, (uint32_t)h->cfg.seed,
-                       (uint32_t)(h->cfg.seed >> 32), h->wind_speed, mask);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("wind_fill_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
-}
-
-// The airframe of every env's (mask: the masked envs') current episode,
-// enqueued on `st`.
-int launch_airframe_fill(dr_handle *h, const uint8_t *mask, hipStream_t st) {
-    const int32_t *ep_num = h->cfg.state_dtype == DR_STATE_F64 ? view_of<double>(h).ep_num
-                                                               : view_of<float>(h).ep_num;
-    hipLaunchKernelGGL(airframe_fill_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->air,
-                       h->stride, h->n, ep_num, h->cfg.env_id_offset, (uint32_t)h->cfg.seed,
-                       (uint32_t)(h->cfg.seed >> 32), var_args<KVAR_AIRFRAME>(h), mask);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("airframe_fill_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
-}
-
-// A new course (j = 0) for every env (mask: the masked envs), enqueued on `st`.
-int launch_waypoint_restart(dr_handle *h, const uint8_t *mask, hipStream_t st) {
-    hipLaunchKernelGGL(waypoint_restart_kernel, dim3(grid_for(h->n)), dim3(kBlock), 0, st, h->wp,
-                       h->n, mask);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("waypoint_restart_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
+    const dim3 grid(grid_for(h->n)), block(kBlock);
+    const uint32_t k0 = (uint32_t)h->cfg.seed, k1 = (uint32_t)(h->cfg.seed >> 32);
+    switch (h->opt_kind) {
+        case dr_handle::OPT_WIND:
+            hipLaunchKernelGGL(wind_fill_kernel, grid, block, 0, st, static_cast<float *>(h->opt),
+                               h->stride, h->n, ep_num, h->cfg.env_id_offset, k0, k1,
+                               h->wind_speed, mask);
+            return launched(h, "wind_fill_kernel");
+        case dr_handle::OPT_AIRFRAME:
+            hipLaunchKernelGGL(airframe_fill_kernel, grid, block, 0, st,
+                               static_cast<float *>(h->opt), h->stride, h->n, ep_num,
+                               h->cfg.env_id_offset, k0, k1, var_args<KVAR_AIRFRAME>(h), mask);
+            return launched(h, "airframe_fill_kernel");
+        case dr_handle::OPT_WAYPOINT:
+            hipLaunchKernelGGL(waypoint_restart_kernel, grid, block, 0, st,
+                               static_cast<int32_t *>(h->opt), h->n, mask);
+            return launched(h, "waypoint_restart_kernel");
+        default: return DR_OK;
+    }
 }
 
 int dispatch_reset(dr_handle *h, const uint8_t *mask, float *obs, int mode,
                    int init, hipStream_t st) {
     return with_state(h, [&](auto s, auto var) {
-        // a wind handle resets as the gym does (the wind is not observed),
-        // then draws the new episodes' mean wind behind it; a waypoint
-        // handle likewise, then starts the new episodes' courses; an
-        // airframe handle likewise, then draws the new episodes' airframes
-        constexpr int V = decltype(var)::value;
-        constexpr int RV = (V == KVAR_WIND || V == KVAR_WAYPOINT || V == KVAR_AIRFRAME)
-                               ? (int)DR_VARIANT_GYM
-                               : V;
-        int rc = launch_reset<typename decltype(s)::type, RV>(h, mask, obs, mode, init, st);
-        if constexpr (V == KVAR_WIND) {
-            if (rc == DR_OK) rc = launch_wind_fill(h, mask, st);
-        }
-        if constexpr (V == KVAR_WAYPOINT) {
-            if (rc == DR_OK) rc = launch_waypoint_restart(h, mask, st);
-        }
-        if constexpr (V == KVAR_AIRFRAME) {
-            if (rc == DR_OK) rc = launch_airframe_fill(h, mask, st);
-        }
+        // an option's handle resets as the gym does (its words are not
+        // observed), then fills the new episodes' words behind it
+        using T = Traits<decltype(var)::value>;
+        int rc = launch_reset<typename decltype(s)::type, T::RESET_VAR>(h, mask, obs, mode, init,
+                                                                        st);
+        if (T::OPTION && rc == DR_OK) rc = launch_option_fill(h, mask, st);
         return rc;
     });
 }
@@ -2967,8 +3009,7 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
     EnvView<S> v = view_of<S>(h);
     const FieldPtrs<S> fp = field_ptrs_of(v);
     const VarArgs<VAR> va = var_args<VAR>(h);
-    bool launched = false;
-    if (!launched && VAR != DR_VARIANT_VECTORIZED && v.host_u) {   // parity mode
+    if (Traits<VAR>::GYMLIKE && v.host_u) {   // parity mode
         if (h->rpw == 32)
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 32, true, false>),
                                dim3(grid_for(h->n, kEnvWpb * 32)), dim3(kEnvBlock), 0, st,
@@ -2977,9 +3018,7 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
             hipLaunchKernelGGL((env_step_kernel<S, VAR, MON, 64, true, false>),
                                dim3(grid_for(h->n, kEnvWpb * 64)), dim3(kEnvBlock), 0, st,
                                v, io, fp, va);
-        launched = true;
-    }
-    if (!launched) {
+    } else {
         const dim3 g64(grid_for(h->n, kEnvWpb * 64)), g32(grid_for(h->n, kEnvWpb * 32));
         switch (h->rpw * 2 + (int)h->nt_loads) {
             case 64:
@@ -2999,10 +3038,7 @@ int launch_step(dr_handle *h, const StepIO &io, hipStream_t st) {
                                    dim3(kEnvBlock), 0, st, v, io, fp, va);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("env_step_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "env_step_kernel");
 }
 
 template <bool MON>
@@ -3028,15 +3064,9 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
         const char *r = std::getenv("DRONERL_ROLLOUT_WS");
         return r ? (std::atoi(r) != 0 ? 1 : 0) : -1;
     }();
-    // The smooth, tag and rk4 variants have the one-role kernel only (the lag
-    // state, the partner exchange and the quaternion step are not built into
-    // the warp-specialised forms), whatever the override says.
-    // (likewise a gym handle with wind: m and g ride in its registers; and one
-    // on a waypoint course: j and q do; and one on randomised airframes: the
-    // six words and two reciprocals do)
-    constexpr bool ONE_ROLE = VAR == DR_VARIANT_SMOOTH || VAR == DR_VARIANT_TAG ||
-                              VAR == DR_VARIANT_RK4 || VAR == KVAR_WIND ||
-                              VAR == KVAR_WAYPOINT || VAR == KVAR_AIRFRAME;
+    // Traits::ONE_ROLE variants have the one-role kernel only, whatever the
+    // override says.
+    constexpr bool ONE_ROLE = Traits<VAR>::ONE_ROLE;
     const bool ws = ONE_ROLE
                         ? false
                         : (ws_env >= 0 ? ws_env == 1
@@ -3076,10 +3106,7 @@ int launch_rollout(dr_handle *h, const RolloutIO &io, hipStream_t st, hipEvent_t
             hipLaunchKernelGGL((env_rollout_kernel<S, VAR, 64, GEN>), grid, block, 0, st, v, io,
                                fp, var_args<VAR>(h));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string("env_rollout_kernel: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "env_rollout_kernel");
 }
 
 template <bool GEN>
@@ -3103,10 +3130,7 @@ int motor_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, fl
                                                     : view_of<float>(h).mot;
     hipLaunchKernelGGL(motor_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
                        mot, h->stride, h->n, ids, k, io, set);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, who);
 }
 
 // DR_FIELD_QUAT of dr_get_state / dr_gather_state / dr_set_state.
@@ -3124,60 +3148,62 @@ int quat_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, voi
         hipLaunchKernelGGL(quat_field_kernel<float>, dim3(grid_for(k)), dim3(kBlock), 0,
                            as_stream(stream), view_of<float>(h), ids, k,
                            static_cast<float *>(io), set);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, who);
 }
 
-// DR_FIELD_WIND of dr_get_state / dr_gather_state / dr_set_state.
-int wind_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, float *io, int set,
-               void *stream) {
-    if (!h->wind)
-        return fail(h, DR_ERR_UNSUPPORTED,
-                    std::string(who) + ": wind exists only after a non-neutral dr_set_wind");
+// The options' fields: which option owns each, what the refusal says while
+// that option is not enabled, and whether its words are i32 (two of them,
+// moved by waypoint_field_kernel) or f32 (six, moved by wind_field_kernel).
+struct OptionField {
+    int field, kind;
+    bool i32;
+    const char *missing;
+};
+constexpr OptionField kOptionFields[] = {
+    {DR_FIELD_WIND, dr_handle::OPT_WIND, false,
+     ": wind exists only after a non-neutral dr_set_wind"},
+    {DR_FIELD_WAYPOINT, dr_handle::OPT_WAYPOINT, true,
+     ": waypoint exists only after dr_set_waypoints"},
+    {DR_FIELD_AIRFRAME, dr_handle::OPT_AIRFRAME, false,
+     ": airframe exists only after a non-neutral dr_set_airframe"}};
+
+// DR_FIELD_WIND / _WAYPOINT / _AIRFRAME of dr_get_state / dr_gather_state /
+// dr_set_state.
+int option_field(dr_handle *h, const char *who, const OptionField &f, const int32_t *ids,
+                 int64_t k, void *io, int set, void *stream) {
+    if (h->opt_kind != f.kind) return fail(h, DR_ERR_UNSUPPORTED, std::string(who) + f.missing);
     if (k == 0) return DR_OK;
     DeviceGuard g(h->cfg.device);
-    hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
-                       h->wind, h->stride, h->n, ids, k, io, set);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return DR_OK;
+    if (f.i32)
+        hipLaunchKernelGGL(waypoint_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0,
+                           as_stream(stream), static_cast<int32_t *>(h->opt), h->stride, h->n,
+                           ids, k, static_cast<int32_t *>(io), set);
+    else
+        hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0,
+                           as_stream(stream), static_cast<float *>(h->opt), h->stride, h->n, ids,
+                           k, static_cast<float *>(io), set);
+    return launched(h, who);
 }
 
-// DR_FIELD_AIRFRAME of dr_get_state / dr_gather_state / dr_set_state: six f32
-// arrays as the wind's, moved by the same kernel.
-int airframe_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, float *io,
-                   int set, void *stream) {
-    if (!h->air)
-        return fail(h, DR_ERR_UNSUPPORTED,
-                    std::string(who) +
-                        ": airframe exists only after a non-neutral dr_set_airframe");
-    if (k == 0) return DR_OK;
-    DeviceGuard g(h->cfg.device);
-    hipLaunchKernelGGL(wind_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0, as_stream(stream),
-                       h->air, h->stride, h->n, ids, k, io, set);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return DR_OK;
-}
-
-// DR_FIELD_WAYPOINT of dr_get_state / dr_gather_state / dr_set_state.
-int waypoint_field(dr_handle *h, const char *who, const int32_t *ids, int64_t k, int32_t *io,
-                   int set, void *stream) {
-    if (!h->wp)
-        return fail(h, DR_ERR_UNSUPPORTED,
-                    std::string(who) + ": waypoint exists only after dr_set_waypoints");
-    if (k == 0) return DR_OK;
-    DeviceGuard g(h->cfg.device);
-    hipLaunchKernelGGL(waypoint_field_kernel, dim3(grid_for(k)), dim3(kBlock), 0,
-                       as_stream(stream), h->wp, h->stride, h->n, ids, k, io, set);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(h, DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return DR_OK;
+// The fields kept beside the state arrays (motor, quat, the options'), for
+// env j (ids null) or env ids[j] of k rows.  False if `field` is none of
+// them; else true, with the call's result in *rc.
+bool side_field(dr_handle *h, const char *who, int field, const int32_t *ids, int64_t k,
+                void *io, int set, void *stream, int *rc) {
+    if (field == DR_FIELD_MOTOR) {
+        *rc = motor_field(h, who, ids, k, static_cast<float *>(io), set, stream);
+        return true;
+    }
+    if (field == DR_FIELD_QUAT) {
+        *rc = quat_field(h, who, ids, k, io, set, stream);
+        return true;
+    }
+    for (const OptionField &f : kOptionFields) {
+        if (field != f.field) continue;
+        *rc = option_field(h, who, f, ids, k, io, set, stream);
+        return true;
+    }
+    return false;
 }
 
 // The rk4 variant keeps a quaternion where the others keep Euler angles.
@@ -3194,6 +3220,45 @@ int check_rng(dr_handle *h) {
         return fail(h, DR_ERR_INVALID,
                     "rng_mode DR_RNG_HOST_UNIFORMS: call dr_set_reset_uniforms first");
     return DR_OK;
+}
+
+// A handle has one of wind, a waypoint course and randomised airframes:
+// `who` (which enables `mine`) is refused while another is enabled.
+int option_conflict(dr_handle *h, const char *who, int mine) {
+    static const char *const kHas[] = {nullptr, ": the handle has wind enabled",
+                                       ": the handle is on a waypoint course",
+                                       ": the handle has airframes enabled"};
+    if (h->opt_kind == dr_handle::OPT_NONE || h->opt_kind == mine) return DR_OK;
+    return fail(h, DR_ERR_UNSUPPORTED, std::string(who) + kHas[h->opt_kind]);
+}
+
+// Enable a filled option (wind, airframe): allocate its six f32 arrays, take
+// the new parameters (`apply`), and give every env's current episode its
+// words now, so that they are a function of (key, env, episode) whenever the
+// option was switched on.  The state may be in use on any stream: drain, fill,
+// drain.  On failure the handle is left without the option.
+template <typename Apply>
+int enable_option(dr_handle *h, int kind, const char *who, Apply &&apply) {
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)6 * h->stride * sizeof(float));
+    if (e != hipSuccess)
+        return fail(h, DR_ERR_NOMEM, std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+    apply();
+    e = hipDeviceSynchronize();
+    h->opt = p;
+    h->opt_kind = kind;
+    int rc = e == hipSuccess ? launch_option_fill(h, nullptr, nullptr)
+                             : fail(h, DR_ERR_HIP, hipGetErrorString(e));
+    if (rc == DR_OK) {
+        e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(h, DR_ERR_HIP, hipGetErrorString(e));
+    }
+    if (rc != DR_OK) {
+        h->opt = nullptr;
+        h->opt_kind = dr_handle::OPT_NONE;
+        (void)hipFree(p);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -3243,14 +3308,8 @@ int dr_create(const dr_config *cfg_in, dr_handle **out) {
     // HBM channel bits); a stride padded to skew them was an A/B build that
     // never became the default.
     h->stride = (cfg.num_envs + 63) / 64 * 64;
-    h->obs_dim = cfg.variant == DR_VARIANT_GYM
-                     ? 15
-                     : (cfg.variant == DR_VARIANT_MOVING
-                            ? 18
-                            : ((cfg.variant == DR_VARIANT_SMOOTH ||
-                                cfg.variant == DR_VARIANT_TAG)
-                                   ? 19
-                                   : (cfg.variant == DR_VARIANT_RK4 ? 16 : 12)));
+    h->obs_dim =
+        for_variant(cfg.variant, [](auto var) { return Traits<decltype(var)::value>::OD; });
     // Launch form by batch size, from the measured sweep
     // (scripts/micro/ab_sweep.sh, profiles/r01_env_launch_sweep.txt):
     // [0, 384k) 64 rows/wave; [384k, 1.5M) 32 + nontemporal state loads;
@@ -3309,9 +3368,7 @@ int dr_destroy(dr_handle *h) {
         // The caller's streams may still use the state: drain first.
         (void)hipDeviceSynchronize();
         (void)hipFree(h->mem);
-        if (h->wind) (void)hipFree(h->wind);
-        if (h->wp) (void)hipFree(h->wp);
-        if (h->air) (void)hipFree(h->air);
+        if (h->opt) (void)hipFree(h->opt);
     }
     delete h;
     return DR_OK;
@@ -3452,17 +3509,8 @@ int dr_rollout_random(dr_handle *h, int32_t k, uint64_t action_seed, int64_t act
 int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_get_state: null handle");
     if (!out) return fail(h, DR_ERR_INVALID, "dr_get_state: out is null");
-    if (field == DR_FIELD_MOTOR)
-        return motor_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
-    if (field == DR_FIELD_QUAT) return quat_field(h, "dr_get_state", nullptr, h->n, out, 0, stream);
-    if (field == DR_FIELD_WIND)
-        return wind_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0, stream);
-    if (field == DR_FIELD_WAYPOINT)
-        return waypoint_field(h, "dr_get_state", nullptr, h->n, static_cast<int32_t *>(out), 0,
-                              stream);
-    if (field == DR_FIELD_AIRFRAME)
-        return airframe_field(h, "dr_get_state", nullptr, h->n, static_cast<float *>(out), 0,
-                              stream);
+    int src;
+    if (side_field(h, "dr_get_state", field, nullptr, h->n, out, 0, stream, &src)) return src;
     if (int rc = euler_refused(h, "dr_get_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_get_state: unknown field");
@@ -3475,26 +3523,15 @@ int dr_get_state(dr_handle *h, int field, void *out, void *stream) {
     else
         hipLaunchKernelGGL(get_field_kernel<float>, dim3(grid_for(h->n)), dim3(kBlock), 0,
                            as_stream(stream), view_of<float>(h), field, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DR_ERR_HIP, std::string("get_field: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "get_field");
 }
 
 int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, void *out,
                     void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_gather_state: null handle");
     if (!env_ids || !out || k < 0) return fail(h, DR_ERR_INVALID, "dr_gather_state: bad arguments");
-    if (field == DR_FIELD_MOTOR)
-        return motor_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
-    if (field == DR_FIELD_QUAT) return quat_field(h, "dr_gather_state", env_ids, k, out, 0, stream);
-    if (field == DR_FIELD_WIND)
-        return wind_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0, stream);
-    if (field == DR_FIELD_WAYPOINT)
-        return waypoint_field(h, "dr_gather_state", env_ids, k, static_cast<int32_t *>(out), 0,
-                              stream);
-    if (field == DR_FIELD_AIRFRAME)
-        return airframe_field(h, "dr_gather_state", env_ids, k, static_cast<float *>(out), 0,
-                              stream);
+    int src;
+    if (side_field(h, "dr_gather_state", field, env_ids, k, out, 0, stream, &src)) return src;
     if (int rc = euler_refused(h, "dr_gather_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_gather_state: unknown field");
@@ -3508,28 +3545,15 @@ int dr_gather_state(dr_handle *h, int field, const int32_t *env_ids, int64_t k, 
     else
         hipLaunchKernelGGL(gather_field_kernel<float>, dim3(grid_for(k)), dim3(kBlock), 0,
                            as_stream(stream), view_of<float>(h), field, env_ids, k, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DR_ERR_HIP, std::string("gather_field: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "gather_field");
 }
 
 int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     if (!h) return fail(nullptr, DR_ERR_INVALID, "dr_set_state: null handle");
     if (!in) return fail(h, DR_ERR_INVALID, "dr_set_state: in is null");
-    if (field == DR_FIELD_MOTOR)
-        return motor_field(h, "dr_set_state", nullptr, h->n,
-                           const_cast<float *>(static_cast<const float *>(in)), 1, stream);
-    if (field == DR_FIELD_QUAT)
-        return quat_field(h, "dr_set_state", nullptr, h->n, const_cast<void *>(in), 1, stream);
-    if (field == DR_FIELD_WIND)
-        return wind_field(h, "dr_set_state", nullptr, h->n,
-                          const_cast<float *>(static_cast<const float *>(in)), 1, stream);
-    if (field == DR_FIELD_WAYPOINT)
-        return waypoint_field(h, "dr_set_state", nullptr, h->n,
-                              const_cast<int32_t *>(static_cast<const int32_t *>(in)), 1, stream);
-    if (field == DR_FIELD_AIRFRAME)
-        return airframe_field(h, "dr_set_state", nullptr, h->n,
-                              const_cast<float *>(static_cast<const float *>(in)), 1, stream);
+    int src;
+    if (side_field(h, "dr_set_state", field, nullptr, h->n, const_cast<void *>(in), 1, stream, &src))
+        return src;
     if (int rc = euler_refused(h, "dr_set_state", field)) return rc;
     if (field < DR_FIELD_POS || field > DR_FIELD_MOTION)
         return fail(h, DR_ERR_INVALID, "dr_set_state: unknown field");
@@ -3542,9 +3566,7 @@ int dr_set_state(dr_handle *h, int field, const void *in, void *stream) {
     else
         hipLaunchKernelGGL(set_field_kernel<float>, dim3(grid_for(h->n)), dim3(kBlock), 0,
                            as_stream(stream), view_of<float>(h), field, in);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, DR_ERR_HIP, std::string("set_field: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(h, "set_field");
 }
 
 int dr_set_reset_uniforms(dr_handle *h, const double *u_dev) {
@@ -3627,46 +3649,21 @@ int dr_set_wind(dr_handle *h, float drag, float wind_speed, float gust_sigma, fl
         return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: max_steps must be below 2^24");
     const bool neutral =
         drag == 0.0f && wind_speed == 0.0f && gust_sigma == 0.0f && gust_rate == 0.0f;
-    // a handle has wind or a waypoint course, not both
-    if (h->wp && !neutral)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: the handle is on a waypoint course");
-    // nor wind and randomised airframes
-    if (h->air && !neutral)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_wind: the handle has airframes enabled");
-    const bool enable = !h->wind && !neutral;
-    float *w = nullptr;
+    if (!neutral)
+        if (int rc = option_conflict(h, "dr_set_wind", dr_handle::OPT_WIND)) return rc;
+    auto apply = [&] {
+        h->drag = drag;
+        h->wind_speed = wind_speed;
+        h->gust_sigma = gust_sigma;
+        h->gust_rate = gust_rate;
+        h->gust_b = 1.0f - gust_rate;
+        h->gust_c = (float)((double)gust_sigma *
+                            std::sqrt(3.0 * (1.0 - (double)h->gust_b * (double)h->gust_b)));
+    };
     DeviceGuard g(h->cfg.device);
-    if (enable) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&w), (size_t)6 * h->stride * sizeof(float));
-        if (e != hipSuccess)
-            return fail(h, DR_ERR_NOMEM,
-                        std::string("dr_set_wind: hipMalloc: ") + hipGetErrorString(e));
-    }
-    h->drag = drag;
-    h->wind_speed = wind_speed;
-    h->gust_sigma = gust_sigma;
-    h->gust_rate = gust_rate;
-    h->gust_b = 1.0f - gust_rate;
-    h->gust_c = (float)((double)gust_sigma *
-                        std::sqrt(3.0 * (1.0 - (double)h->gust_b * (double)h->gust_b)));
-    if (enable) {
-        // every env's current episode gets its mean wind now, so that it is
-        // a function of (key, env, episode) whenever wind was switched on;
-        // the state may have been written on any stream: drain, fill, drain
-        hipError_t e = hipDeviceSynchronize();
-        h->wind = w;
-        int rc = e == hipSuccess ? launch_wind_fill(h, nullptr, nullptr)
-                                 : fail(h, DR_ERR_HIP, hipGetErrorString(e));
-        if (rc == DR_OK) {
-            e = hipDeviceSynchronize();
-            if (e != hipSuccess) rc = fail(h, DR_ERR_HIP, hipGetErrorString(e));
-        }
-        if (rc != DR_OK) {
-            h->wind = nullptr;
-            (void)hipFree(w);
-            return rc;
-        }
-    }
+    if (h->opt_kind != dr_handle::OPT_WIND && !neutral)
+        return enable_option(h, dr_handle::OPT_WIND, "dr_set_wind", apply);
+    apply();
     return DR_OK;
 }
 
@@ -3692,15 +3689,12 @@ int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus) {
     if (h->cfg.variant != DR_VARIANT_GYM)
         return fail(h, DR_ERR_UNSUPPORTED,
                     "dr_set_waypoints: only DR_VARIANT_GYM has waypoint courses");
-    if (h->wind)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: the handle has wind enabled");
-    if (h->air)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: the handle has airframes enabled");
+    if (int rc = option_conflict(h, "dr_set_waypoints", dr_handle::OPT_WAYPOINT)) return rc;
     // the waypoint counter carries the index, below the step limit, in its
     // low 24 bits
     if (h->cfg.max_steps >= (1 << 24))
         return fail(h, DR_ERR_UNSUPPORTED, "dr_set_waypoints: max_steps must be below 2^24");
-    if (!h->wp) {
+    if (h->opt_kind != dr_handle::OPT_WAYPOINT) {
         // j = q = 0 for every env; the state may be in use on any stream:
         // drain, allocate and clear, drain
         DeviceGuard g(h->cfg.device);
@@ -3718,7 +3712,8 @@ int dr_set_waypoints(dr_handle *h, float reach_radius, float reach_bonus) {
             (void)hipFree(w);
             return fail(h, DR_ERR_HIP, hipGetErrorString(e));
         }
-        h->wp = w;
+        h->opt = w;
+        h->opt_kind = dr_handle::OPT_WAYPOINT;
     }
     h->reach_radius = reach_radius;
     h->reach_bonus = reach_bonus;
@@ -3745,48 +3740,25 @@ int dr_set_airframe(dr_handle *h, float mass_spread, float inertia_spread, float
     if (h->cfg.variant != DR_VARIANT_GYM)
         return fail(h, DR_ERR_UNSUPPORTED,
                     "dr_set_airframe: only DR_VARIANT_GYM has airframe randomisation");
-    // a handle has one of wind, a waypoint course and randomised airframes
-    if (h->wind)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_airframe: the handle has wind enabled");
-    if (h->wp)
-        return fail(h, DR_ERR_UNSUPPORTED, "dr_set_airframe: the handle is on a waypoint course");
+    if (int rc = option_conflict(h, "dr_set_airframe", dr_handle::OPT_AIRFRAME)) return rc;
     const bool neutral = mass_spread == 0.0f && inertia_spread == 0.0f && motor_spread == 0.0f;
-    const bool enable = !h->air && !neutral;
-    float *a = nullptr;
-    DeviceGuard g(h->cfg.device);
-    if (enable) {
-        hipError_t e =
-            hipMalloc(reinterpret_cast<void **>(&a), (size_t)6 * h->stride * sizeof(float));
-        if (e != hipSuccess)
-            return fail(h, DR_ERR_NOMEM,
-                        std::string("dr_set_airframe: hipMalloc: ") + hipGetErrorString(e));
-    }
     const float old[3] = {h->mass_spread, h->inertia_spread, h->motor_spread};
-    h->mass_spread = mass_spread;
-    h->inertia_spread = inertia_spread;
-    h->motor_spread = motor_spread;
-    if (enable) {
-        // every env's current episode gets its airframe now, so that the
-        // field is a function of (key, env, episode) whenever the option was
-        // switched on; the state may be in use on any stream: drain, fill,
-        // drain
-        hipError_t e = hipDeviceSynchronize();
-        h->air = a;
-        int rc = e == hipSuccess ? launch_airframe_fill(h, nullptr, nullptr)
-                                 : fail(h, DR_ERR_HIP, hipGetErrorString(e));
-        if (rc == DR_OK) {
-            e = hipDeviceSynchronize();
-            if (e != hipSuccess) rc = fail(h, DR_ERR_HIP, hipGetErrorString(e));
-        }
+    auto apply = [&] {
+        h->mass_spread = mass_spread;
+        h->inertia_spread = inertia_spread;
+        h->motor_spread = motor_spread;
+    };
+    DeviceGuard g(h->cfg.device);
+    if (h->opt_kind != dr_handle::OPT_AIRFRAME && !neutral) {
+        const int rc = enable_option(h, dr_handle::OPT_AIRFRAME, "dr_set_airframe", apply);
         if (rc != DR_OK) {
-            h->air = nullptr;
             h->mass_spread = old[0];
             h->inertia_spread = old[1];
             h->motor_spread = old[2];
-            (void)hipFree(a);
-            return rc;
         }
+        return rc;
     }
+    apply();
     return DR_OK;
 }
 
@@ -3809,10 +3781,7 @@ int dr_random_actions(int64_t n, uint64_t seed, int64_t env_id_offset,
                        as_stream(stream), n, (uint32_t)seed, (uint32_t)(seed >> 32),
                        env_id_offset, (uint64_t)step, lo, hi - lo,
                        reinterpret_cast<float4 *>(out));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(nullptr, DR_ERR_HIP, std::string("random_actions: ") + hipGetErrorString(e));
-    return DR_OK;
+    return launched(nullptr, "random_actions");
 }
 
 #if DR_STAMPS
