@@ -34,6 +34,9 @@ DR_STATE_F64 = 0
 DR_STATE_F32 = 1
 DR_RNG_PHILOX = 0
 DR_RNG_HOST_UNIFORMS = 1
+DR_VECNORM_OBS = 1
+DR_VECNORM_REWARD = 2
+DR_VECNORM_TRAINING = 4
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
@@ -164,6 +167,12 @@ SIGNATURES = {
     "dr_gemm_x6_bwd_first_rows": (c_int64, [c_int64]),
     "dr_linear_tanh2_x6": (c_int, [c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, _P]),
+    "dr_vecnorm_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "dr_vecnorm_init": (c_int, [c_int64, c_int64, _P, _P, _P, _P]),
+    "dr_vecnorm_step": (c_int, [c_int64, c_int64, _P, _P, _P, _P, c_int, c_double, c_double,
+                                c_double, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "dr_vecnorm_apply": (c_int, [c_int64, c_int64, _P, _P, c_double, c_double, _P, _P]),
+    "dr_vecnorm_unapply": (c_int, [c_int64, c_int64, _P, _P, c_double, _P, _P]),
 }
 
 _lib = None

@@ -196,6 +196,18 @@ __device__ inline float tanh_fast(float x) {
 #endif
 }
 
+// Chan et al. merge of (n, mean, M2) b into a (the advantage statistics of
+// ppo_kernels.hip and the running moments of vecnorm.hip).
+__device__ inline void chan_merge(double &n, double &mu, double &M2, double nb_, double mb,
+                                  double m2b) {
+    const double tot = n + nb_;
+    if (tot == 0.0) return;
+    const double dl = mb - mu;
+    mu += dl * nb_ / tot;
+    M2 += m2b + dl * dl * n * nb_ / tot;
+    n = tot;
+}
+
 // Compute units of the current device, looked up once per device index (a
 // process may drive handles on several GPUs).
 inline int device_cu_count() {

@@ -676,17 +676,6 @@ __global__ __launch_bounds__(kBlock) void gather_records_kernel(
     }
 }
 
-// Chan et al. merge of (n, mean, M2) b into a.
-__device__ inline void chan_merge(double &n, double &mu, double &M2, double nb_, double mb,
-                                  double m2b) {
-    const double tot = n + nb_;
-    if (tot == 0.0) return;
-    const double dl = mb - mu;
-    mu += dl * nb_ / tot;
-    M2 += m2b + dl * dl * n * nb_ / tot;
-    n = tot;
-}
-
 // Combine the per-block (n, mean, M2) partials with the whole block: strided
 // per-thread merges, then a fixed-shape tree in LDS (deterministic).  Every
 // thread returns the result.  Needs blockDim.x == kBlock.
@@ -2750,3 +2739,6 @@ int dr_first_layer_backward2(int64_t m, int64_t k, int64_t n, const float *x,
 }
 
 }  // extern "C"
+
+// VecNormalize (dr_vecnorm_*): its own file, this translation unit.
+#include "vecnorm.hip"

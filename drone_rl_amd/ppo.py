@@ -121,6 +121,17 @@ class PPOConfig:
     mass_spread: float = 0.0
     inertia_spread: float = 0.0
     motor_spread: float = 0.0
+    # SB3's VecNormalize around the env, both off by
+    # default: running f64 statistics of the observations / of the discounted
+    # returns on the device, the policy and the value head see
+    # clip((obs - mean) / sqrt(var + eps), +-clip_obs) and
+    # clip(rew / sqrt(ret_var + eps), +-clip_reward); the monitor's episode
+    # returns stay raw.  One GPU only (no merge of moments across ranks)
+    normalize_obs: bool = False
+    normalize_reward: bool = False
+    clip_obs: float = 10.0
+    clip_reward: float = 10.0
+    norm_epsilon: float = 1e-8
 
     def __post_init__(self):
         from .env import (OBS_DIM, check_airframe, check_smoothing, check_tag, check_waypoints,
@@ -134,6 +145,7 @@ class PPOConfig:
         course = check_waypoints(self.variant, self.reach_radius, self.reach_bonus, wind=wind)
         check_airframe(self.variant, self.mass_spread, self.inertia_spread, self.motor_spread,
                        wind=wind, waypoints=course)
+        K.check_vecnorm(self.clip_obs, self.clip_reward, self.norm_epsilon, self.gamma)
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -151,6 +163,9 @@ class PPOTrainer:
         self.cfg = cfg
         self.rank, self.world = rank, world_size
         self.pg = process_group
+        if world_size > 1 and (cfg.normalize_obs or cfg.normalize_reward):
+            raise ValueError("normalize_obs / normalize_reward need world_size 1: the running "
+                             "statistics are not merged across ranks")
         self.device = torch.device("cuda", torch.cuda.current_device()) \
             if device is None else torch.device(device)
         N, T = cfg.num_envs, cfg.n_steps
@@ -263,9 +278,44 @@ class PPOTrainer:
         self._ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         # optional TrajectoryTensorboardCallback equivalent (trajectory.py)
         self.trajectory = None
-        self.env.reset(self.obs[0])
+        # VecNormalize (off: nothing allocated, the launches of before)
+        self.vecnorm = None
+        if cfg.normalize_obs or cfg.normalize_reward:
+            self._enable_vecnorm(cfg.normalize_obs, cfg.normalize_reward, cfg.clip_obs,
+                                 cfg.clip_reward, cfg.norm_epsilon)
+        self._reset_env()
         if self.world > 1:
             self.sync_params()
+
+    # ----------------------------------------------------------- VecNormalize
+    def _enable_vecnorm(self, norm_obs, norm_reward, clip_obs, clip_reward, epsilon):
+        """Put the normaliser between the env and the rollout buffers: the env
+        writes into per-step raw scratch, the normaliser writes obs[t + 1] and
+        rewards[t]."""
+        if self.world > 1:
+            raise ValueError("normalize_obs / normalize_reward need world_size 1")
+        N, od, dev = self.cfg.num_envs, self.env.obs_dim, self.device
+        self.vecnorm = K.VecNormalize(N, od, dev, gamma=self.cfg.gamma, clip_obs=clip_obs,
+                                      clip_reward=clip_reward, epsilon=epsilon,
+                                      norm_obs=norm_obs, norm_reward=norm_reward)
+        self._raw_obs = torch.zeros(N, od, dtype=torch.float32, device=dev)
+        self._raw_rew = torch.zeros(N, dtype=torch.float32, device=dev)
+        # bootstrap_timeouts: the normalised terminal obs V(term) is taken on
+        self._term_norm = torch.zeros(N, od, dtype=torch.float32, device=dev) \
+            if self.cfg.bootstrap_timeouts else None
+        self.cfg = dataclasses.replace(self.cfg, normalize_obs=bool(norm_obs),
+                                       normalize_reward=bool(norm_reward),
+                                       clip_obs=float(clip_obs), clip_reward=float(clip_reward),
+                                       norm_epsilon=float(epsilon))
+        self._rgraph = None
+
+    def _reset_env(self):
+        """Reset every env into obs[0] (through the normaliser when on)."""
+        if self.vecnorm is None:
+            self.env.reset(self.obs[0])
+        else:
+            self.env.reset(self._raw_obs)
+            self.vecnorm.reset(self._raw_obs, out=self.obs[0])
 
     # ------------------------------------------------------------ DP plumbing
     def sync_params(self):
@@ -343,13 +393,24 @@ class PPOTrainer:
             # VecMonitor outputs land in this step's slice (done rows only)
             self.env.ep_ret = self.ep_ret[t]
             self.env.ep_len = self.ep_len[t]
-            self.env.step(self.act_env, obs_out=self.obs[t + 1], rew_out=self.rewards[t],
+            vn = self.vecnorm
+            self.env.step(self.act_env, obs_out=self.obs[t + 1] if vn is None else self._raw_obs,
+                          rew_out=self.rewards[t] if vn is None else self._raw_rew,
                           done_out=self.dones[t + 1],
                           trunc_out=None if self.trunc is None else self.trunc[t])
+            term = self.env.term_obs
+            if vn is not None:
+                # VecNormalize.step_wait: raw scratch -> the rollout buffers
+                # (the terminal obs of done envs normalised for V(term))
+                vn.step(self._raw_obs, self._raw_rew, self.dones[t + 1],
+                        term_obs=term if self.trunc is not None else None,
+                        obs_out=self.obs[t + 1], rew_out=self.rewards[t],
+                        term_out=self._term_norm if self.trunc is not None else None)
+                term = self._term_norm
             if self.trunc is not None:
                 # SB3 collect_rollouts: rewards[idx] += gamma * V(terminal
                 # obs) for envs whose episode was truncated at the limit
-                _, v_term = fwd(self.env.term_obs)
+                _, v_term = fwd(term)
                 self.rewards[t].add_(torch.where(self.trunc[t].bool(),
                                                  v_term * self.cfg.gamma, 0.0))
             if self.trajectory is not None:
@@ -364,14 +425,16 @@ class PPOTrainer:
         as on the eager path."""
         c = self.cfg
         if kind == "rollout":
-            e = self.env
+            e, v = self.env, self.vecnorm
             # (the wind values also say which kernels the env launches)
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
                     e.wind_enabled, e.drag, e.wind_speed, e.gust_sigma, e.gust_rate,
                     e.waypoints_enabled, e.reach_radius, e.reach_bonus,
                     e.airframe_enabled, e.mass_spread, e.inertia_spread, e.motor_spread,
                     self.env.tag_radius, self.env.crash_penalty,
-                    self.env.motor_alpha, self.env.rate_penalty)
+                    self.env.motor_alpha, self.env.rate_penalty) + \
+                (() if self.vecnorm is None else
+                 (v.flags(), v.gamma, v.clip_obs, v.clip_reward, v.epsilon))
         o = self.opt
         return (c.seed, self.rank, c.n_epochs, c.batch_size, c.clip_range, c.ent_coef,
                 c.vf_coef, c.normalize_advantage, float(o.lr), o.b1, o.b2, o.eps,
@@ -657,7 +720,10 @@ class PPOTrainer:
         SB3 .zip does NOT save (drone.py:18,33), rollout continuation, and
         the counters that key every Philox stream."""
         T = self.cfg.n_steps
+        # (last_obs is what the policy saw: normalised when the option is on)
+        extra = {} if self.vecnorm is None else {"vecnorm": self.vecnorm.state_dict()}
         return {
+            **extra,
             "config": dataclasses.asdict(self.cfg),
             "flat": self.policy.flat.detach().cpu().clone(),
             "policy": self.policy.state_dict(),
@@ -695,6 +761,14 @@ class PPOTrainer:
                                         ("mass_spread", "inertia_spread", "motor_spread")))
             for k, v in sd["env"].items():
                 self.env.set(k, v)
+            if "vecnorm" in sd:
+                vs = sd["vecnorm"]
+                if self.vecnorm is None:
+                    # likewise a checkpoint with statistics: its normalisation
+                    self._enable_vecnorm(vs["norm_obs"], vs["norm_reward"], vs["clip_obs"],
+                                         vs["clip_reward"], vs["epsilon"])
+                self.vecnorm.load_state_dict(vs)
+                self._rgraph = None
             self.obs[0].copy_(sd["last_obs"].to(self.device))
             self.dones[T].copy_(sd["last_dones"].to(self.device))
         self._rolled = False
@@ -717,7 +791,7 @@ class PPOTrainer:
         self._rolled = False
         self.dones[self.cfg.n_steps].fill_(1)
         with torch.no_grad():
-            self.env.reset(self.obs[0])
+            self._reset_env()
         return ck
 
     def close(self):

@@ -456,3 +456,202 @@ class GradFinish:
         ws = self._workspace(device)
         check(_lib.lib().dr_grad_finish_run(ctypes.byref(self.desc), ptr(ws), ws.numel(),
                                             torch.cuda.current_stream(device).cuda_stream))
+
+
+def check_vecnorm(clip_obs, clip_reward, epsilon, gamma=0.99):
+    """The value rules of dr_vecnorm_step, raised as ValueError on the host."""
+    import math
+    for name, v in (("clip_obs", clip_obs), ("clip_reward", clip_reward)):
+        if not (isinstance(v, (int, float)) and math.isfinite(v) and v > 0):
+            raise ValueError(f"{name} must be > 0 and finite, got {v!r}")
+    if not (isinstance(epsilon, (int, float)) and math.isfinite(epsilon) and epsilon >= 0):
+        raise ValueError(f"epsilon must be >= 0 and finite, got {epsilon!r}")
+    if not (isinstance(gamma, (int, float)) and math.isfinite(gamma)):
+        raise ValueError(f"gamma must be finite, got {gamma!r}")
+
+
+class VecNormalize:
+    """stable-baselines3's VecNormalize on device tensors (dr_vecnorm_*,
+    DESIGN.md section 21): running f64 statistics of the observations and of
+    the discounted returns, advanced and applied by at most three launches per
+    step with no host round trip, so a captured rollout can hold it.
+
+    State: obs_rms f64 (1 + 2 D,) = count, mean, var; ret_rms f64 (3,);
+    returns f64 (n,).  `training` False freezes the statistics (evaluation)."""
+
+    NPZ_KEYS = ("obs_count", "obs_mean", "obs_var", "ret_count", "ret_mean", "ret_var",
+                "clip_obs", "clip_reward", "gamma", "epsilon")
+
+    def __init__(self, n: int, obs_dim: int, device, gamma=0.99, clip_obs=10.0, clip_reward=10.0,
+                 epsilon=1e-8, norm_obs=True, norm_reward=True):
+        check_vecnorm(clip_obs, clip_reward, epsilon, gamma)
+        if n < 1 or not 1 <= obs_dim <= 24:
+            raise ValueError("VecNormalize needs n >= 1 and 1 <= obs_dim <= 24")
+        self.n, self.obs_dim, self.device = int(n), int(obs_dim), torch.device(device)
+        self.gamma, self.clip_obs, self.clip_reward = float(gamma), float(clip_obs), \
+            float(clip_reward)
+        self.epsilon = float(epsilon)
+        self.norm_obs, self.norm_reward = bool(norm_obs), bool(norm_reward)
+        self.training = True
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.obs_rms = torch.empty(1 + 2 * self.obs_dim, **f64)
+        self.ret_rms = torch.empty(3, **f64)
+        self.returns = torch.empty(self.n, **f64)
+        nbytes = _lib.lib().dr_vecnorm_workspace_bytes(self.n, self.obs_dim)
+        self.ws = torch.empty(max(nbytes // 8, 1), **f64)
+        check(_lib.lib().dr_vecnorm_init(self.n, self.obs_dim, ptr(self.obs_rms),
+                                         ptr(self.ret_rms), ptr(self.returns),
+                                         _s(self.obs_rms)))
+
+    # views of the statistics (device tensors, no copy)
+    @property
+    def obs_count(self):
+        return self.obs_rms[0]
+
+    @property
+    def obs_mean(self):
+        return self.obs_rms[1:1 + self.obs_dim]
+
+    @property
+    def obs_var(self):
+        return self.obs_rms[1 + self.obs_dim:]
+
+    def flags(self) -> int:
+        return ((_lib.DR_VECNORM_OBS if self.norm_obs else 0) |
+                (_lib.DR_VECNORM_REWARD if self.norm_reward else 0) |
+                (_lib.DR_VECNORM_TRAINING if self.training else 0))
+
+    def _rows(self, t, what):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), \
+            f"{what}: expected a contiguous f32 device tensor"
+        assert t.dim() == 2 and t.shape[1] == self.obs_dim, f"{what}: expected (rows, obs_dim)"
+        return t
+
+    def _step(self, obs, rew, done, term_obs, obs_out, rew_out, term_out):
+        check(_lib.lib().dr_vecnorm_step(
+            self.n, self.obs_dim, ptr(obs), ptr(rew), ptr(done), ptr(term_obs), self.flags(),
+            self.gamma, self.clip_obs, self.clip_reward, self.epsilon, ptr(self.obs_rms),
+            ptr(self.ret_rms), ptr(self.returns), ptr(obs_out), ptr(rew_out), ptr(term_out),
+            ptr(self.ws), self.ws.numel() * 8, _s(obs)))
+
+    def reset(self, obs, out=None):
+        """VecNormalize.reset on the raw reset observations (n, obs_dim):
+        returns <- 0, the statistics advance (training), out = normalised."""
+        assert self._rows(obs, "obs").shape[0] == self.n
+        o = torch.empty_like(obs) if out is None else self._rows(out, "out")
+        assert o.shape == obs.shape
+        self._step(obs, None, None, None, o, None, None)
+        return o
+
+    def step(self, obs, rew, done, term_obs=None, obs_out=None, rew_out=None, term_out=None):
+        """VecNormalize.step_wait on one raw env step: obs (n, obs_dim) f32,
+        rew (n,) f32, done (n,) u8, term_obs (n, obs_dim) f32 whose rows of
+        done envs hold the terminal observations.  Outputs may alias their
+        inputs.  Returns (obs_out, rew_out) or, with term_obs, also term_out
+        (rows of envs that are not done are left as they were)."""
+        assert self._rows(obs, "obs").shape[0] == self.n
+        assert rew.dtype == torch.float32 and rew.is_contiguous() and rew.shape == (self.n,)
+        assert done.dtype == torch.uint8 and done.is_contiguous() and done.shape == (self.n,)
+        o = torch.empty_like(obs) if obs_out is None else self._rows(obs_out, "obs_out")
+        r = torch.empty_like(rew) if rew_out is None else rew_out
+        assert o.shape == obs.shape and r.shape == rew.shape and r.dtype == torch.float32 \
+            and r.is_contiguous()
+        if term_obs is None:
+            assert term_out is None, "term_out needs term_obs"
+            self._step(obs, rew, done, None, o, r, None)
+            return o, r
+        assert self._rows(term_obs, "term_obs").shape == obs.shape
+        to = torch.empty_like(term_obs) if term_out is None else self._rows(term_out, "term_out")
+        assert to.shape == obs.shape
+        self._step(obs, rew, done, term_obs, o, r, to)
+        return o, r, to
+
+    def normalize_obs(self, obs, out=None):
+        """Normalise m rows (any m) with the statistics as they are (a copy
+        when norm_obs is off)."""
+        self._rows(obs, "obs")
+        o = torch.empty_like(obs) if out is None else self._rows(out, "out")
+        assert o.shape == obs.shape
+        if not self.norm_obs:
+            if o.data_ptr() != obs.data_ptr():
+                o.copy_(obs)
+            return o
+        check(_lib.lib().dr_vecnorm_apply(obs.shape[0], self.obs_dim, ptr(obs), ptr(self.obs_rms),
+                                          self.clip_obs, self.epsilon, ptr(o), _s(obs)))
+        return o
+
+    def unnormalize_obs(self, obs, out=None):
+        """The inverse of normalize_obs up to the clip."""
+        self._rows(obs, "obs")
+        o = torch.empty_like(obs) if out is None else self._rows(out, "out")
+        assert o.shape == obs.shape
+        if not self.norm_obs:
+            if o.data_ptr() != obs.data_ptr():
+                o.copy_(obs)
+            return o
+        check(_lib.lib().dr_vecnorm_unapply(obs.shape[0], self.obs_dim, ptr(obs),
+                                            ptr(self.obs_rms), self.epsilon, ptr(o), _s(obs)))
+        return o
+
+    # ------------------------------------------------------------ checkpoint
+    def state_dict(self):
+        return {"obs_rms": self.obs_rms.cpu().clone(), "ret_rms": self.ret_rms.cpu().clone(),
+                "returns": self.returns.cpu().clone(), "gamma": self.gamma,
+                "clip_obs": self.clip_obs, "clip_reward": self.clip_reward,
+                "epsilon": self.epsilon, "norm_obs": self.norm_obs,
+                "norm_reward": self.norm_reward, "training": self.training}
+
+    def load_state_dict(self, sd):
+        if tuple(sd["obs_rms"].shape) != tuple(self.obs_rms.shape):
+            raise ValueError("VecNormalize: the checkpoint's obs_dim differs")
+        check_vecnorm(sd["clip_obs"], sd["clip_reward"], sd["epsilon"], sd["gamma"])
+        self.obs_rms.copy_(sd["obs_rms"].to(self.device))
+        self.ret_rms.copy_(sd["ret_rms"].to(self.device))
+        if tuple(sd["returns"].shape) == tuple(self.returns.shape):
+            self.returns.copy_(sd["returns"].to(self.device))
+        else:                       # another env count: the statistics carry over
+            self.returns.zero_()
+        self.gamma, self.clip_obs = float(sd["gamma"]), float(sd["clip_obs"])
+        self.clip_reward, self.epsilon = float(sd["clip_reward"]), float(sd["epsilon"])
+        self.norm_obs, self.norm_reward = bool(sd["norm_obs"]), bool(sd["norm_reward"])
+        self.training = bool(sd.get("training", True))
+
+    def npz_dict(self):
+        """The statistics and settings as numpy values (NPZ_KEYS)."""
+        import numpy as np
+        o, r, D = self.obs_rms.cpu().numpy(), self.ret_rms.cpu().numpy(), self.obs_dim
+        return {"obs_count": np.float64(o[0]), "obs_mean": o[1:1 + D].copy(),
+                "obs_var": o[1 + D:].copy(), "ret_count": np.float64(r[0]),
+                "ret_mean": np.float64(r[1]), "ret_var": np.float64(r[2]),
+                "clip_obs": np.float64(self.clip_obs), "clip_reward": np.float64(self.clip_reward),
+                "gamma": np.float64(self.gamma), "epsilon": np.float64(self.epsilon),
+                "norm_obs": np.bool_(self.norm_obs), "norm_reward": np.bool_(self.norm_reward)}
+
+    def load_npz_dict(self, z):
+        import numpy as np
+        D = self.obs_dim
+        mean, var = np.asarray(z["obs_mean"], np.float64), np.asarray(z["obs_var"], np.float64)
+        if mean.shape != (D,) or var.shape != (D,):
+            raise ValueError("VecNormalize: the file's obs_dim differs")
+        check_vecnorm(float(z["clip_obs"]), float(z["clip_reward"]), float(z["epsilon"]),
+                      float(z["gamma"]))
+        o = np.concatenate([[float(z["obs_count"])], mean, var])
+        r = np.array([float(z["ret_count"]), float(z["ret_mean"]), float(z["ret_var"])])
+        self.obs_rms.copy_(torch.from_numpy(o).to(self.device))
+        self.ret_rms.copy_(torch.from_numpy(r).to(self.device))
+        self.returns.zero_()
+        self.clip_obs, self.clip_reward = float(z["clip_obs"]), float(z["clip_reward"])
+        self.gamma, self.epsilon = float(z["gamma"]), float(z["epsilon"])
+        if "norm_obs" in z:
+            self.norm_obs, self.norm_reward = bool(z["norm_obs"]), bool(z["norm_reward"])
+
+    def save_npz(self, path):
+        """obs / ret count, mean and var, the clips, gamma and epsilon as one
+        .npz (how to copy them into an SB3 VecNormalize)."""
+        import numpy as np
+        np.savez(path, **self.npz_dict())
+
+    def load_npz(self, path):
+        import numpy as np
+        with np.load(path) as z:
+            self.load_npz_dict(z)

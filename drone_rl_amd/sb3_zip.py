@@ -46,6 +46,7 @@ import torch
 from .policy import ActorCritic, _sb3_name
 
 SB3_VERSION = "2.3.2"
+VECNORM_MEMBER = "dronerl_vecnormalize.npz"
 
 # ----------------------------------------------------------------- naming
 
@@ -243,6 +244,12 @@ def save(trainer, path):
         buf = io.BytesIO()
         np.savez(buf, **env)
         z.writestr("dronerl_env_state.npz", buf.getvalue())
+        if getattr(trainer, "vecnorm", None) is not None:
+            # the VecNormalize statistics (SB3 pickles its wrapper beside the
+            # model; INTEGRATION.md: how to copy these into one)
+            buf = io.BytesIO()
+            np.savez(buf, **trainer.vecnorm.npz_dict())
+            z.writestr(VECNORM_MEMBER, buf.getvalue())
 
 
 # ---------------------------------------------------------------- reading
@@ -264,6 +271,9 @@ def read(path):
         if "dronerl_env_state.npz" in names:
             with np.load(io.BytesIO(z.read("dronerl_env_state.npz"))) as f:
                 out["env"] = {k: f[k] for k in f.files}
+        if VECNORM_MEMBER in names:
+            with np.load(io.BytesIO(z.read(VECNORM_MEMBER))) as f:
+                out["vecnorm"] = {k: f[k] for k in f.files}
     if out["policy"] is None:
         raise ValueError(f"{path}: no policy.pth member (not an SB3 checkpoint)")
     return out
@@ -314,6 +324,13 @@ def load_into(trainer, path, load_env_state=True):
             len(ck["env"]["ep_num"]) == trainer.env.num_envs:
         trainer.env.set("ep_num", ck["env"]["ep_num"])
         trainer.env.set("eps", ck["env"]["eps"])
+    vn = ck.get("vecnorm")
+    if vn is not None:
+        if trainer.vecnorm is None:
+            trainer._enable_vecnorm(bool(vn.get("norm_obs", True)),
+                                    bool(vn.get("norm_reward", True)), float(vn["clip_obs"]),
+                                    float(vn["clip_reward"]), float(vn["epsilon"]))
+        trainer.vecnorm.load_npz_dict(vn)
     return ck
 
 

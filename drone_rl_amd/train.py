@@ -48,7 +48,7 @@ def resume_path(path: str, rank: int, world: int) -> str | None:
     return None
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--total-steps", type=float, default=2e6 * 64)
@@ -117,7 +117,21 @@ def main(argv=None):
                     help="after a resume, train --total-steps more (SB3's default, the "
                          "reference's behaviour); --no-reset-num-timesteps trains up to "
                          "--total-steps in all")
-    a = ap.parse_args(argv)
+    ap.add_argument("--normalize-obs", action="store_true",
+                    help="SB3 VecNormalize: running mean / variance normalisation of the "
+                         "observations (one GPU)")
+    ap.add_argument("--normalize-reward", action="store_true",
+                    help="SB3 VecNormalize: rewards divided by the running std of the "
+                         "discounted returns (one GPU)")
+    ap.add_argument("--clip-obs", type=float, default=10.0,
+                    help="bound of the normalised observations")
+    ap.add_argument("--clip-reward", type=float, default=10.0,
+                    help="bound of the normalised rewards")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -135,6 +149,8 @@ def main(argv=None):
                   reach_radius=a.reach_radius, reach_bonus=a.reach_bonus,
                   mass_spread=a.mass_spread, inertia_spread=a.inertia_spread,
                   motor_spread=a.motor_spread,
+                  normalize_obs=a.normalize_obs, normalize_reward=a.normalize_reward,
+                  clip_obs=a.clip_obs, clip_reward=a.clip_reward,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

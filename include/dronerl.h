@@ -830,6 +830,79 @@ int dr_linear_tanh2_x6(int64_t m, int64_t k, int64_t n, const float *x, const in
                        const float *b1, float *h1, const float *w256, void *img, void *ximg,
                        void *stream);
 
+/* ---------------------------------------------------------------------------
+ * VecNormalize: stable-baselines3's running
+ * observation / reward normalisation with its statistics as device state, so
+ * that it can sit inside a captured rollout.  All buffers are device memory.
+ *
+ * A RunningMeanStd is (count, mean, var) in f64, initially (1e-4, 0, 1).  Its
+ * update over the N rows of a batch takes per column bm = mean(x), bv = the
+ * population variance of x, bc = N, and sets
+ *     d = bm - mean;  tot = count + bc;
+ *     mean <- mean + d * bc / tot;
+ *     var  <- (var * count + bv * bc + d * d * count * bc / tot) / tot;
+ *     count <- tot.
+ * State: obs_rms f64[1 + 2 D] = count, mean[D], var[D]; ret_rms f64[3] =
+ * count, mean, var; returns f64[N], the running discounted return per env.
+ *
+ * dr_vecnorm_step, in this order (flags: DR_VECNORM_*):
+ *   1. TRAINING and OBS: obs_rms.update(obs), the f32 values widened exactly;
+ *   2. obs_out = f32(clip((f64(obs) - mean) / sqrt(var + epsilon), -clip_obs,
+ *      clip_obs)) with the statistics as they now are (OBS off: a copy);
+ *   3. TRAINING and REWARD: returns <- returns * gamma + rewards, then
+ *      ret_rms.update(returns) over all N envs, done ones included (SB3
+ *      updates ret_rms whenever training but reads it only with REWARD: here
+ *      it stays untouched without REWARD);
+ *   4. rew_out = f32(clip(f64(rewards) / sqrt(ret_var + epsilon),
+ *      -clip_reward, clip_reward)) (REWARD off: a copy);
+ *   5. with terminal_obs: rows of done envs are normalised as in 2 into
+ *      terminal_obs_out; rows of envs that are not done are left untouched;
+ *   6. returns[done] <- 0.
+ * rewards == NULL is the reset form: returns <- 0 for every env, then 1 and 2
+ * (dones and the terminal buffers must be NULL too).  obs_out may be obs and
+ * rew_out may be rewards (in place).  The moments are one pass of per-block
+ * (n, mean, M2) partials merged in a fixed order (Chan et al.), all in f64,
+ * bv = M2 / N: results depend on the inputs alone and are bitwise equal from
+ * run to run and under graph replay.  At most three launches, no host sync, no
+ * atomics; nothing is kept in `workspace` between calls.
+ * Non-finite inputs get no special treatment: a NaN or inf in a column poisons
+ * that column's statistics for good, as in SB3, and the clip passes NaN on.
+ *
+ * DR_ERR_INVALID, before any HIP call, with a dr_last_error(NULL) message:
+ * n or m < 1, obs_dim outside [1, 24], a clip that is not > 0 and finite,
+ * epsilon < 0 or non-finite, a non-finite gamma, unknown flag bits, a missing
+ * buffer, or a workspace smaller than dr_vecnorm_workspace_bytes(n, obs_dim).
+ * These additions break no caller: DR_ABI_VERSION stays 16.
+ * ------------------------------------------------------------------------- */
+enum dr_vecnorm_flags {
+    DR_VECNORM_OBS = 1,       /* normalise observations                      */
+    DR_VECNORM_REWARD = 2,    /* normalise rewards                           */
+    DR_VECNORM_TRAINING = 4   /* advance the statistics                      */
+};
+
+size_t dr_vecnorm_workspace_bytes(int64_t n, int64_t obs_dim);
+
+/* obs_rms <- (1e-4, 0, 1), ret_rms <- (1e-4, 0, 1), returns <- 0. */
+int dr_vecnorm_init(int64_t n, int64_t obs_dim, double *obs_rms, double *ret_rms,
+                    double *returns, void *stream);
+
+int dr_vecnorm_step(int64_t n, int64_t obs_dim, const float *obs, const float *rewards,
+                    const uint8_t *dones, const float *terminal_obs, int flags, double gamma,
+                    double clip_obs, double clip_reward, double epsilon, double *obs_rms,
+                    double *ret_rms, double *returns, float *obs_out, float *rew_out,
+                    float *terminal_obs_out, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
+/* Step 2 alone on m rows (any m) with frozen statistics: evaluation, and the
+   minibatches of callers that keep raw observations. */
+int dr_vecnorm_apply(int64_t m, int64_t obs_dim, const float *obs, const double *obs_rms,
+                     double clip_obs, double epsilon, float *obs_out, void *stream);
+
+/* VecNormalize.unnormalize_obs: obs_out = f32(f64(obs_norm) * sqrt(var +
+   epsilon) + mean) on m rows (the clip is not undone). */
+int dr_vecnorm_unapply(int64_t m, int64_t obs_dim, const float *obs_norm, const double *obs_rms,
+                       double epsilon, float *obs_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

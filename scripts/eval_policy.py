@@ -44,6 +44,11 @@ airframe is not observed, so any gym policy can be put on any airframe.
 --fixed-airframe m,s,g0,g1,g2,g3 flies every env and every episode on that one
 airframe instead (written through set("airframe") ahead of each step).
 
+A checkpoint with VecNormalize statistics ("vecnorm")
+is evaluated through them, frozen: the policy sees normalize_obs(obs) of the
+raw env's observations, and every reported reward is the env's raw one.
+--no-normalize feeds the raw observations instead.
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
                                 [--drag 0.5 --wind-speed 2 --gust-sigma 0.5 --gust-rate 0.1]
                                 [--reach-radius 0.25 --reach-bonus 1]
@@ -94,9 +99,25 @@ def course_of(cfg, args):
     return r, b
 
 
+def frozen_normaliser(sd, envs, obs_dim, dev, normalize=True):
+    """obs -> what the policy was trained on: the checkpoint's VecNormalize
+    statistics, frozen (the identity for a checkpoint without them)."""
+    if not normalize or "vecnorm" not in sd:
+        return lambda obs: obs
+    from drone_rl_amd import ppo_kernels as K
+    vs = sd["vecnorm"]
+    vn = K.VecNormalize(envs, obs_dim, dev, gamma=vs["gamma"], clip_obs=vs["clip_obs"],
+                        clip_reward=vs["clip_reward"], epsilon=vs["epsilon"])
+    vn.load_state_dict(vs)      # (returns of another env count are dropped)
+    vn.training = False
+    buf = torch.empty(envs, obs_dim, dtype=torch.float32, device=dev)
+    return lambda obs: vn.normalize_obs(obs, out=buf)
+
+
 @torch.no_grad()
 def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0),
-             course=(None, None), airframe=(0.0, 0.0, 0.0), fixed_airframe=None):
+             course=(None, None), airframe=(0.0, 0.0, 0.0), fixed_airframe=None,
+             normalize=True):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -122,6 +143,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     env.set("eps", torch.full((envs,), float(eps), dtype=torch.float64))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
+    norm = frozen_normaliser(sd, envs, OBS_DIM[variant], dev, normalize)
     g = torch.Generator(device=dev).manual_seed(seed)
     std = pol.log_std.exp()
     ret_sum = len_sum = n_done = n_crash = 0.0
@@ -132,7 +154,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     ep_ret = torch.empty(envs, device=dev)
     ep_len = torch.empty(envs, dtype=torch.int32, device=dev)
     for _ in range(steps):
-        mean, _ = infer(obs)
+        mean, _ = infer(norm(obs))
         a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
                                                                  device=dev)
         env.ep_ret, env.ep_len = ep_ret, ep_len
@@ -168,7 +190,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
 
 
 @torch.no_grad()
-def evaluate_tag(ckpt, envs, steps, seed, deterministic):
+def evaluate_tag(ckpt, envs, steps, seed, deterministic, normalize=True):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -179,6 +201,7 @@ def evaluate_tag(ckpt, envs, steps, seed, deterministic):
                      crash_penalty=cfg.get("crash_penalty"))
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
+    norm = frozen_normaliser(sd, envs, OBS_DIM["tag"], dev, normalize)
     g = torch.Generator(device=dev).manual_seed(seed)
     std = pol.log_std.exp()
     ep_ret = torch.empty(envs, device=dev)
@@ -189,7 +212,7 @@ def evaluate_tag(ckpt, envs, steps, seed, deterministic):
     crashed = [0.0, 0.0]
     len_sum = tagged = dist = 0.0
     for _ in range(steps):
-        mean, _ = infer(obs)
+        mean, _ = infer(norm(obs))
         a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
                                                                  device=dev)
         env.ep_ret, env.ep_len = ep_ret, ep_len
@@ -240,9 +263,15 @@ def main():
     ap.add_argument("--fixed-airframe", default=None,
                     help="gym checkpoints: m,s,g0,g1,g2,g3 -- fly every episode on this one "
                          "airframe (not together with the spreads)")
+    ap.add_argument("--no-normalize", action="store_true",
+                    help="checkpoints with VecNormalize statistics: feed the policy the raw "
+                         "observations instead of the normalised ones")
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
-    cfg = torch.load(a.ckpt, map_location="cpu", weights_only=True)["config"]
+    sd = torch.load(a.ckpt, map_location="cpu", weights_only=True)
+    cfg = sd["config"]
+    if "vecnorm" in sd:
+        out["normalized"] = not a.no_normalize
     out["variant"] = cfg.get("variant", "gym")
     if out["variant"] == "smooth":
         out["motor_alpha"] = cfg.get("motor_alpha", 1.0)
@@ -278,9 +307,10 @@ def main():
             out["fixed_airframe"] = fixed
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (
-            evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det) if out["variant"] == "tag"
+            evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det, not a.no_normalize)
+            if out["variant"] == "tag"
             else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind, course, airframe,
-                          fixed))
+                          fixed, not a.no_normalize))
     print(json.dumps(out), flush=True)
 
 
