@@ -8,6 +8,7 @@ a one-env batch.  The SB3 / gymnasium vector facades live in vec_env.py.
 from __future__ import annotations
 
 import ctypes
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -46,6 +47,14 @@ _I32_ROW_FIELDS = {"waypoint": 2}
 # dr_set_waypoints' defaults where only one of the two values is given
 REACH_RADIUS = 0.25
 REACH_BONUS = 1.0
+# the gym options that exclude each other (a handle has one option slot), by
+# ENV_OPTIONS name, and the refusal of each pair
+EXCLUSIONS = {
+    frozenset(("wind", "waypoints")): "a gym env has wind or a waypoint course, not both",
+    frozenset(("wind", "airframe")): "a gym env has wind or randomised airframes, not both",
+    frozenset(("waypoints", "airframe")):
+        "a gym env has a waypoint course or randomised airframes, not both",
+}
 
 
 def quat_to_euler(q) -> np.ndarray:
@@ -145,7 +154,7 @@ def check_waypoints(variant: str, reach_radius=None, reach_bonus=None,
     if max_steps is not None and int(max_steps) >= 1 << 24:
         raise ValueError("waypoint courses need max_steps below 2^24")
     if wind is not None and any(float(w) != 0.0 for w in wind):
-        raise ValueError("a gym env has wind or a waypoint course, not both")
+        raise ValueError(EXCLUSIONS[frozenset(("wind", "waypoints"))])
     return r, b
 
 
@@ -170,9 +179,9 @@ def check_airframe(variant: str, mass_spread=0.0, inertia_spread=0.0, motor_spre
             raise ValueError("mass_spread / inertia_spread / motor_spread need variant='gym', "
                              f"not {variant!r}")
         if wind is not None and any(float(w) != 0.0 for w in wind):
-            raise ValueError("a gym env has wind or randomised airframes, not both")
+            raise ValueError(EXCLUSIONS[frozenset(("wind", "airframe"))])
         if waypoints is not None:
-            raise ValueError("a gym env has a waypoint course or randomised airframes, not both")
+            raise ValueError(EXCLUSIONS[frozenset(("waypoints", "airframe"))])
     return tuple(vals)
 
 
@@ -197,6 +206,95 @@ def check_tag(variant: str, tag_radius, crash_penalty, num_envs: int | None = No
         raise ValueError("variant='tag' pairs env 2j with env 2j+1: num_envs and env_id_offset "
                          f"must be even, got {num_envs!r} and {env_id_offset!r}")
     return r, c
+
+
+class EnvOption(NamedTuple):
+    """One optional mechanism of the env, as every Python layer reads it."""
+    name: str
+    variant: str        # the variant that owns it
+    keys: tuple         # its keywords, in the order of its check_* and set_*
+    defaults: tuple     # ... and their values where the option is off
+    idle: tuple         # what DroneBatch's attributes of those names read while it is off
+    field: str | None   # the state field it enables ("<name>_enabled" says whether it has)
+    check: Callable     # check_*(variant, *values, **context)
+    context: tuple      # the keywords of check_env_options its check_* also takes
+    setter: str         # the DroneBatch method that applies it
+    help: tuple         # one command-line help text per keyword
+
+
+ENV_OPTIONS = (
+    EnvOption("smoothing", "smooth", ("motor_alpha", "rate_penalty"), (1.0, 0.0), (1.0, 0.0),
+              None, check_smoothing, (), "set_smoothing",
+              ("--variant smooth: lag blend dt / (tau + dt) in (0, 1] (1 = no lag)",
+               "--variant smooth: penalty on |command - motor force|^2 per step")),
+    EnvOption("tag", "tag", ("tag_radius", "crash_penalty"), (None, None),
+              (TAG_RADIUS, CRASH_PENALTY), None, check_tag, ("num_envs", "env_id_offset"),
+              "set_tag",
+              ("--variant tag: the pursuer's bonus radius in m (default 0.25)",
+               "--variant tag: what a crashing drone pays (default 0)")),
+    EnvOption("wind", "gym", ("drag", "wind_speed", "gust_sigma", "gust_rate"), (0.0,) * 4,
+              (0.0,) * 4, "wind", check_wind, ("max_steps",), "set_wind",
+              ("--variant gym: linear drag per unit mass in 1/s (0 = vacuum)",
+               "--variant gym: bound of each axis of the per-episode mean wind, m/s",
+               "--variant gym: stationary std of each gust axis, m/s",
+               "--variant gym: the gusts' per-step mean reversion in [0, 1]")),
+    EnvOption("waypoints", "gym", ("reach_radius", "reach_bonus"), (None, None), (0.0, 0.0),
+              "waypoint", check_waypoints, ("max_steps",), "set_waypoints",
+              ("--variant gym: fly waypoint courses; the target moves on inside "
+               "this distance (default 0.25 when only --reach-bonus is given)",
+               "--variant gym: reward added in the step of a reach (default 1.0 "
+               "when only --reach-radius is given)")),
+    EnvOption("airframe", "gym", ("mass_spread", "inertia_spread", "motor_spread"), (0.0,) * 3,
+              (0.0,) * 3, "airframe", check_airframe, (), "set_airframe",
+              ("--variant gym: per-episode mass scale drawn in 1 +- this, in [0, 0.9]",
+               "--variant gym: per-episode inertia scale drawn in 1 +- this",
+               "--variant gym: per-episode gain of each motor drawn in 1 +- this")),
+)
+ENV_OPTION_KEYS = tuple(k for o in ENV_OPTIONS for k in o.keys)
+ENV_OPTION = {o.name: o for o in ENV_OPTIONS}
+
+
+def _excluded(name: str, others) -> None:
+    """Refuse option `name` beside any of the options `others` that excludes it."""
+    for other in others:
+        if frozenset((name, other)) in EXCLUSIONS:
+            raise ValueError(EXCLUSIONS[frozenset((name, other))])
+
+
+def check_env_options(variant: str, options: dict, *, num_envs=None, env_id_offset=0,
+                      max_steps=None, last=()) -> dict:
+    """Every option's check_* on the keywords in `options` (a missing one is
+    at its default), in table order with the options named in `last` behind
+    the others, then the exclusions: raised as ValueError before any device
+    work.  Returns, per option name, the values its set_* takes, or None where
+    the option is off (a variant's own parameters are on with the variant, a
+    gym option with a value off neutral)."""
+    context = {"num_envs": num_envs, "env_id_offset": env_id_offset, "max_steps": max_steps}
+    checked = {}
+    for o in sorted(ENV_OPTIONS, key=lambda o: o.name in last):
+        given = tuple(options.get(k, d) for k, d in zip(o.keys, o.defaults))
+        vals = o.check(variant, *given, **{k: context[k] for k in o.context})
+        if o.field is None:
+            vals = (given if vals is None else vals) if variant == o.variant else None
+        elif vals is not None and any(vals):
+            _excluded(o.name, (n for n, v in checked.items() if v is not None))
+        else:
+            vals = None
+        checked[o.name] = vals
+    return checked
+
+
+def add_option_arguments(parser, first=()) -> None:
+    """One --flag per option keyword, off by default, in table order with the
+    options named in `first` ahead of the others."""
+    for o in sorted(ENV_OPTIONS, key=lambda o: o.name not in first):
+        for k, d, h in zip(o.keys, o.defaults, o.help):
+            parser.add_argument("--" + k.replace("_", "-"), type=float, default=d, help=h)
+
+
+def option_values(namespace) -> dict:
+    """The option keywords of a namespace add_option_arguments' parser filled."""
+    return {k: getattr(namespace, k) for k in ENV_OPTION_KEYS}
 
 
 def _stream(device):
@@ -260,23 +358,16 @@ class DroneBatch:
                  dtype: torch.dtype = torch.float64, device=None, seed: int = 0,
                  auto_reset: bool = True, rng: str = "philox",
                  env_id_offset: int = 0, max_steps: int | None = None,
-                 keep_terminal_obs: bool = False, monitor: bool = False,
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
-                 tag_radius: float | None = None, crash_penalty: float | None = None,
-                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None,
-                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
-                 motor_spread: float = 0.0):
+                 keep_terminal_obs: bool = False, monitor: bool = False, **options):
+        for k in options:
+            if k not in ENV_OPTION_KEYS:
+                raise TypeError(f"DroneBatch.__init__() got an unexpected keyword argument '{k}'")
         if variant not in OBS_DIM:
             raise ValueError(f"unknown variant {variant!r}")
-        check_smoothing(variant, motor_alpha, rate_penalty)
-        wind = check_wind(variant, drag, wind_speed, gust_sigma, gust_rate, max_steps)
-        course = check_waypoints(variant, reach_radius, reach_bonus, max_steps, wind)
-        airframe = check_airframe(variant, mass_spread, inertia_spread, motor_spread,
-                                  wind=wind, waypoints=course)
-        tag_radius, crash_penalty = check_tag(variant, tag_radius, crash_penalty, num_envs,
-                                              env_id_offset)
+        # (the tag rules last: the order these refusals have always come in)
+        options = check_env_options(variant, options, num_envs=num_envs,
+                                    env_id_offset=env_id_offset, max_steps=max_steps,
+                                    last=("tag",))
         if dtype not in (torch.float64, torch.float32):
             raise ValueError("dtype must be torch.float64 or torch.float32")
         if rng not in ("philox", "host"):
@@ -317,24 +408,13 @@ class DroneBatch:
         self.ep_ret = torch.zeros(n, dtype=torch.float32, device=dev) if monitor else None
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev) if monitor else None
         self._uniforms = None
-        self.motor_alpha, self.rate_penalty = 1.0, 0.0
-        if variant == "smooth":
-            self.set_smoothing(motor_alpha, rate_penalty)
-        self.tag_radius, self.crash_penalty = TAG_RADIUS, CRASH_PENALTY
-        if variant == "tag":
-            self.set_tag(tag_radius, crash_penalty)
-        self.drag = self.wind_speed = self.gust_sigma = self.gust_rate = 0.0
-        self.wind_enabled = False
-        self.reach_radius = self.reach_bonus = 0.0
-        self.waypoints_enabled = False
-        self.mass_spread = self.inertia_spread = self.motor_spread = 0.0
-        self.airframe_enabled = False
-        if any(wind):
-            self.set_wind(*wind)
-        if course is not None:
-            self.set_waypoints(*course)
-        if any(airframe):
-            self.set_airframe(*airframe)
+        for o in ENV_OPTIONS:
+            self.__dict__.update(zip(o.keys, o.idle))
+            if o.field is not None:
+                setattr(self, o.name + "_enabled", False)
+        for o in ENV_OPTIONS:
+            if options[o.name] is not None:
+                getattr(self, o.setter)(*options[o.name])
 
     # -- lifecycle -------------------------------------------------------
     def close(self):
@@ -598,13 +678,41 @@ class DroneBatch:
         self.seed_value = int(seed)
         check(self.L.dr_set_seed(self.handle, self.seed_value & (2**64 - 1)), self.handle)
 
+    def _check_set(self, name: str, *values):
+        """What every set_* refuses, as ValueError before any device work: a
+        batch of another variant, the option's argument rules and, where the
+        values would switch a gym option on, an enabled option that excludes
+        it.  Returns its check_*'s result."""
+        o = ENV_OPTION[name]
+        if self.variant != o.variant:
+            raise ValueError(f"{o.setter} needs variant={o.variant!r}, not {self.variant!r}")
+        context = {"max_steps": self.max_steps} if "max_steps" in o.context else {}
+        vals = o.check(self.variant, *values, **context)
+        if o.field is not None and any(vals):
+            _excluded(name, (e.name for e in self._enabled_options()))
+        return vals
+
+    def option_state(self) -> tuple:
+        """Per option in table order, its values and, where it has a state
+        field, whether it is enabled: everything about the options that a
+        captured graph holds (the kernels launched and their arguments)."""
+        return tuple(tuple(getattr(self, k) for k in o.keys) +
+                     ((getattr(self, o.name + "_enabled"),) if o.field is not None else ())
+                     for o in ENV_OPTIONS)
+
+    def _enabled_options(self) -> list:
+        return [o for o in ENV_OPTIONS
+                if o.field is not None and getattr(self, o.name + "_enabled")]
+
+    def option_fields(self) -> tuple:
+        """The state fields of the enabled options, in table order."""
+        return tuple(o.field for o in self._enabled_options())
+
     def set_smoothing(self, motor_alpha: float, rate_penalty: float) -> None:
         """variant="smooth": new lag blend and action-rate penalty for every
         step / rollout enqueued after the call (a captured graph keeps the
         values it was captured with)."""
-        if self.variant != "smooth":
-            raise ValueError(f"set_smoothing needs variant='smooth', not {self.variant!r}")
-        check_smoothing(self.variant, motor_alpha, rate_penalty)
+        self._check_set("smoothing", motor_alpha, rate_penalty)
         check(self.L.dr_set_smoothing(self.handle, float(motor_alpha), float(rate_penalty)),
               self.handle)
         self.motor_alpha, self.rate_penalty = float(motor_alpha), float(rate_penalty)
@@ -614,9 +722,7 @@ class DroneBatch:
         """variant="tag": new tag radius and crash penalty (None = the default)
         for every step / rollout enqueued after the call (a captured graph
         keeps the values it was captured with)."""
-        if self.variant != "tag":
-            raise ValueError(f"set_tag needs variant='tag', not {self.variant!r}")
-        r, c = check_tag(self.variant, tag_radius, crash_penalty)
+        r, c = self._check_set("tag", tag_radius, crash_penalty)
         check(self.L.dr_set_tag(self.handle, r, c), self.handle)
         # what the kernels see: the f32 values
         rr, cc = ctypes.c_float(), ctypes.c_float()
@@ -632,13 +738,7 @@ class DroneBatch:
         draws every env's mean wind for its current episode: it waits for the
         device and must not be made while a graph is being captured (a
         captured graph keeps the kernels and values it was captured with)."""
-        if self.variant != "gym":
-            raise ValueError(f"set_wind needs variant='gym', not {self.variant!r}")
-        w = check_wind(self.variant, drag, wind_speed, gust_sigma, gust_rate, self.max_steps)
-        if self.waypoints_enabled and any(w):
-            raise ValueError("a gym env has wind or a waypoint course, not both")
-        if self.airframe_enabled and any(w):
-            raise ValueError("a gym env has wind or randomised airframes, not both")
+        w = self._check_set("wind", drag, wind_speed, gust_sigma, gust_rate)
         check(self.L.dr_set_wind(self.handle, *w), self.handle)
         self.drag, self.wind_speed, self.gust_sigma, self.gust_rate = w
         self.wind_enabled = self.wind_enabled or any(w)
@@ -652,14 +752,9 @@ class DroneBatch:
         must not be made while a graph is being captured (a captured graph
         keeps the kernels and values it was captured with).  The option
         cannot be switched off again."""
-        if self.variant != "gym":
-            raise ValueError(f"set_waypoints needs variant='gym', not {self.variant!r}")
         if reach_radius is None and reach_bonus is None:
             reach_radius = REACH_RADIUS
-        rb = check_waypoints(self.variant, reach_radius, reach_bonus, self.max_steps,
-                             (1.0,) if self.wind_enabled else None)
-        if self.airframe_enabled:
-            raise ValueError("a gym env has a waypoint course or randomised airframes, not both")
+        rb = self._check_set("waypoints", reach_radius, reach_bonus)
         check(self.L.dr_set_waypoints(self.handle, *rb), self.handle)
         self.reach_radius, self.reach_bonus = rb
         self.waypoints_enabled = True
@@ -674,11 +769,7 @@ class DroneBatch:
         while a graph is being captured (a captured graph keeps the kernels
         and values it was captured with).  All zeros on a batch that never
         enabled the option enables nothing."""
-        if self.variant != "gym":
-            raise ValueError(f"set_airframe needs variant='gym', not {self.variant!r}")
-        a = check_airframe(self.variant, mass_spread, inertia_spread, motor_spread,
-                           wind=(1.0,) if self.wind_enabled else None,
-                           waypoints=(0.0, 0.0) if self.waypoints_enabled else None)
+        a = self._check_set("airframe", mass_spread, inertia_spread, motor_spread)
         if (self.wind_enabled or self.waypoints_enabled) and not any(a):
             return   # neutral on a handle that carries another option: nothing to do
         check(self.L.dr_set_airframe(self.handle, *a), self.handle)

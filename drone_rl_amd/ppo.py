@@ -36,7 +36,8 @@ import torch
 
 from . import dist as D
 from . import ppo_kernels as K
-from .env import MOTOR_MAX, DroneBatch
+from .env import (ENV_OPTION_KEYS, ENV_OPTIONS, MOTOR_MAX, OBS_DIM, DroneBatch,
+                  check_env_options)
 from .policy import ActorCritic, FusedTrainStep, PolicyInference, fusable, use_tuned_gemms
 
 
@@ -134,18 +135,14 @@ class PPOConfig:
     norm_epsilon: float = 1e-8
 
     def __post_init__(self):
-        from .env import (OBS_DIM, check_airframe, check_smoothing, check_tag, check_waypoints,
-                          check_wind)
         if self.variant not in OBS_DIM:
             raise ValueError(f"unknown variant {self.variant!r}")
-        check_smoothing(self.variant, self.motor_alpha, self.rate_penalty)
-        check_tag(self.variant, self.tag_radius, self.crash_penalty, self.num_envs)
-        wind = check_wind(self.variant, self.drag, self.wind_speed, self.gust_sigma,
-                          self.gust_rate)
-        course = check_waypoints(self.variant, self.reach_radius, self.reach_bonus, wind=wind)
-        check_airframe(self.variant, self.mass_spread, self.inertia_spread, self.motor_spread,
-                       wind=wind, waypoints=course)
+        check_env_options(self.variant, self.env_options(), num_envs=self.num_envs)
         K.check_vecnorm(self.clip_obs, self.clip_reward, self.norm_epsilon, self.gamma)
+
+    def env_options(self) -> dict:
+        """The env's option keywords (env.ENV_OPTIONS) as DroneBatch takes them."""
+        return {k: getattr(self, k) for k in ENV_OPTION_KEYS}
 
     @classmethod
     def sb3_defaults(cls, **kw):
@@ -179,13 +176,7 @@ class PPOTrainer:
                               env_id_offset=D.env_shard(rank, N)[0], monitor=True,
                               keep_terminal_obs=cfg.bootstrap_timeouts,
                               dtype=torch.float64 if cfg.state_dtype == "f64" else torch.float32,
-                              motor_alpha=cfg.motor_alpha, rate_penalty=cfg.rate_penalty,
-                              tag_radius=cfg.tag_radius, crash_penalty=cfg.crash_penalty,
-                              drag=cfg.drag, wind_speed=cfg.wind_speed,
-                              gust_sigma=cfg.gust_sigma, gust_rate=cfg.gust_rate,
-                              reach_radius=cfg.reach_radius, reach_bonus=cfg.reach_bonus,
-                              mass_spread=cfg.mass_spread, inertia_spread=cfg.inertia_spread,
-                              motor_spread=cfg.motor_spread)
+                              **cfg.env_options())
         # waypoint courses: the reaches of the last rollout (device scalar)
         self._wp_gain = None
         if cfg.initial_eps:
@@ -425,14 +416,12 @@ class PPOTrainer:
         as on the eager path."""
         c = self.cfg
         if kind == "rollout":
-            e, v = self.env, self.vecnorm
-            # (the wind values also say which kernels the env launches)
-            return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps,
-                    e.wind_enabled, e.drag, e.wind_speed, e.gust_sigma, e.gust_rate,
-                    e.waypoints_enabled, e.reach_radius, e.reach_bonus,
-                    e.airframe_enabled, e.mass_spread, e.inertia_spread, e.motor_spread,
-                    self.env.tag_radius, self.env.crash_penalty,
-                    self.env.motor_alpha, self.env.rate_penalty) + \
+            v = self.vecnorm
+            # every env option (their values also say which kernels the env
+            # launches), the last one first: the variants' own parameters
+            # close the key
+            return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps) + \
+                tuple(x for o in reversed(self.env.option_state()) for x in o) + \
                 (() if self.vecnorm is None else
                  (v.flags(), v.gamma, v.clip_obs, v.clip_reward, v.epsilon))
         o = self.opt
@@ -709,9 +698,7 @@ class PPOTrainer:
         # (a gym env carries its wind once enabled)
         return self._ENV_FIELDS + {"moving": ("motion",),
                                    "smooth": ("motor",)}.get(self.cfg.variant, ()) + \
-            (("wind",) if self.env.wind_enabled else ()) + \
-            (("waypoint",) if self.env.waypoints_enabled else ()) + \
-            (("airframe",) if self.env.airframe_enabled else ())
+            self.env.option_fields()
 
     def state_dict(self):
         """Everything needed to resume bit-for-bit on the same device count:
@@ -746,19 +733,12 @@ class PPOTrainer:
             self.opt.m.copy_(sd["adam"]["exp_avg"].to(self.device))
             self.opt.v.copy_(sd["adam"]["exp_avg_sq"].to(self.device))
             self.opt.t = int(sd["adam"]["step"])
-            if "wind" in sd["env"] and not self.env.wind_enabled:
-                # a wind checkpoint into a trainer built without wind: take
-                # the checkpoint's conditions
-                self.env.set_wind(*(sd["config"].get(k, 0.0) for k in
-                                    ("drag", "wind_speed", "gust_sigma", "gust_rate")))
-            if "waypoint" in sd["env"] and not self.env.waypoints_enabled:
-                # likewise a waypoint checkpoint: the checkpoint's course
-                self.env.set_waypoints(sd["config"].get("reach_radius"),
-                                       sd["config"].get("reach_bonus"))
-            if "airframe" in sd["env"] and not self.env.airframe_enabled:
-                # likewise an airframe checkpoint: the checkpoint's spreads
-                self.env.set_airframe(*(sd["config"].get(k, 0.0) for k in
-                                        ("mass_spread", "inertia_spread", "motor_spread")))
+            for o in ENV_OPTIONS:
+                if o.field in sd["env"] and o.field not in self.env.option_fields():
+                    # a checkpoint with an option's field into a trainer built
+                    # without the option: take the checkpoint's values
+                    getattr(self.env, o.setter)(*(sd["config"].get(k, d)
+                                                  for k, d in zip(o.keys, o.defaults)))
             for k, v in sd["env"].items():
                 self.env.set(k, v)
             if "vecnorm" in sd:

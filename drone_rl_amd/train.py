@@ -19,6 +19,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from .env import add_option_arguments, option_values
 from .ppo import PPOConfig, PPOTrainer
 
 
@@ -66,34 +67,8 @@ def build_parser():
                          "smooth = gym behind a motor lag with an action-rate penalty; "
                          "tag = pursuer / evader pairs, self-play with one shared policy; "
                          "rk4 = the gym task on a quaternion attitude with an RK4 step")
-    ap.add_argument("--tag-radius", type=float, default=None,
-                    help="--variant tag: the pursuer's bonus radius in m (default 0.25)")
-    ap.add_argument("--crash-penalty", type=float, default=None,
-                    help="--variant tag: what a crashing drone pays (default 0)")
-    ap.add_argument("--motor-alpha", type=float, default=1.0,
-                    help="--variant smooth: lag blend dt / (tau + dt) in (0, 1] (1 = no lag)")
-    ap.add_argument("--rate-penalty", type=float, default=0.0,
-                    help="--variant smooth: penalty on |command - motor force|^2 per step")
-    ap.add_argument("--drag", type=float, default=0.0,
-                    help="--variant gym: linear drag per unit mass in 1/s (0 = vacuum)")
-    ap.add_argument("--wind-speed", type=float, default=0.0,
-                    help="--variant gym: bound of each axis of the per-episode mean wind, m/s")
-    ap.add_argument("--gust-sigma", type=float, default=0.0,
-                    help="--variant gym: stationary std of each gust axis, m/s")
-    ap.add_argument("--gust-rate", type=float, default=0.0,
-                    help="--variant gym: the gusts' per-step mean reversion in [0, 1]")
-    ap.add_argument("--reach-radius", type=float, default=None,
-                    help="--variant gym: fly waypoint courses; the target moves on inside "
-                         "this distance (default 0.25 when only --reach-bonus is given)")
-    ap.add_argument("--reach-bonus", type=float, default=None,
-                    help="--variant gym: reward added in the step of a reach (default 1.0 "
-                         "when only --reach-radius is given)")
-    ap.add_argument("--mass-spread", type=float, default=0.0,
-                    help="--variant gym: per-episode mass scale drawn in 1 +- this, in [0, 0.9]")
-    ap.add_argument("--inertia-spread", type=float, default=0.0,
-                    help="--variant gym: per-episode inertia scale drawn in 1 +- this")
-    ap.add_argument("--motor-spread", type=float, default=0.0,
-                    help="--variant gym: per-episode gain of each motor drawn in 1 +- this")
+    # every env option's flags (the tag ones first, where --help has listed them)
+    add_option_arguments(ap, first=("tag",))
     ap.add_argument("--sb3-defaults", action="store_true",
                     help="SB3 PPO defaults of the reference (n_steps 2048, batch 64, 64x64)")
     ap.add_argument("--checkpoint", default="./dd_gpu.pt")
@@ -141,14 +116,7 @@ def main(argv=None):
     common = dict(num_envs=a.envs, learning_rate=a.lr, ent_coef=a.ent_coef, seed=a.seed,
                   grad_buckets=a.grad_buckets,
                   state_dtype=a.state_dtype, variant=a.variant, initial_eps=a.initial_eps,
-                  bootstrap_timeouts=a.bootstrap_timeouts,
-                  motor_alpha=a.motor_alpha, rate_penalty=a.rate_penalty,
-                  tag_radius=a.tag_radius, crash_penalty=a.crash_penalty,
-                  drag=a.drag, wind_speed=a.wind_speed, gust_sigma=a.gust_sigma,
-                  gust_rate=a.gust_rate,
-                  reach_radius=a.reach_radius, reach_bonus=a.reach_bonus,
-                  mass_spread=a.mass_spread, inertia_spread=a.inertia_spread,
-                  motor_spread=a.motor_spread,
+                  bootstrap_timeouts=a.bootstrap_timeouts, **option_values(a),
                   normalize_obs=a.normalize_obs, normalize_reward=a.normalize_reward,
                   clip_obs=a.clip_obs, clip_reward=a.clip_reward,
                   eps_schedule=tuple((int(u), float(e)) for u, e in

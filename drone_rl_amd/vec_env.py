@@ -48,30 +48,20 @@ _INFO_TEMPLATE = {"TimeLimit.truncated": False}
 
 
 class BatchedDroneVecEnv(_VecEnvBase):
-    """N DroneGymEnv envs on one GPU behind the SB3 VecEnv API."""
+    """N DroneGymEnv envs on one GPU behind the SB3 VecEnv API.  `env_options`
+    are the variants' and the gym env's option keywords, as DroneBatch
+    documents them."""
 
     def __init__(self, num_envs: int = 1, variant: str = "gym",
                  dtype: torch.dtype = torch.float64, device=None, seed: int | None = None,
                  monitor: bool = True, rng: str = "philox", env_id_offset: int = 0,
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
-                 tag_radius: float | None = None, crash_penalty: float | None = None,
-                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None,
-                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
-                 motor_spread: float = 0.0):
+                 **env_options):
         if seed is None:
             seed = int(np.random.randint(0, 2**31 - 1))
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=(variant != "vectorized"), rng=rng,
                                 env_id_offset=env_id_offset, keep_terminal_obs=True,
-                                monitor=True, motor_alpha=motor_alpha,
-                                rate_penalty=rate_penalty, tag_radius=tag_radius,
-                                crash_penalty=crash_penalty, drag=drag, wind_speed=wind_speed,
-                                gust_sigma=gust_sigma, gust_rate=gust_rate,
-                                reach_radius=reach_radius, reach_bonus=reach_bonus,
-                                mass_spread=mass_spread, inertia_spread=inertia_spread,
-                                motor_spread=motor_spread)
+                                monitor=True, **env_options)
         self._monitor = monitor
         od = self.batch.obs_dim
         obs_space = make_box(-np.inf, np.inf, (od,), np.float32)
@@ -222,28 +212,20 @@ class DroneVectorEnv:
     infos carries "final_obs" / "final_info" / "_final_obs" masks, and
     "episode" {"r","l"} arrays like gymnasium's RecordEpisodeStatistics.
     `as_tensors=True` returns device tensors instead of numpy arrays.
+    `env_options` are the wrapped variants' option keywords, as DroneBatch
+    documents them.
     """
 
     metadata = {"autoreset_mode": "SameStep"}
 
     def __init__(self, num_envs: int, device=None, seed: int = 0,
                  dtype: torch.dtype = torch.float64, split_time_limit: bool = False,
-                 as_tensors: bool = False, variant: str = "gym",
-                 motor_alpha: float = 1.0, rate_penalty: float = 0.0,
-                 drag: float = 0.0, wind_speed: float = 0.0, gust_sigma: float = 0.0,
-                 gust_rate: float = 0.0,
-                 reach_radius: float | None = None, reach_bonus: float | None = None,
-                 mass_spread: float = 0.0, inertia_spread: float = 0.0,
-                 motor_spread: float = 0.0):
+                 as_tensors: bool = False, variant: str = "gym", **env_options):
         if variant not in ("gym", "smooth", "rk4"):
             raise ValueError("DroneVectorEnv wraps the 'gym', 'smooth' or 'rk4' variant")
         self.batch = DroneBatch(num_envs, variant, dtype=dtype, device=device, seed=seed,
                                 auto_reset=True, keep_terminal_obs=True, monitor=True,
-                                motor_alpha=motor_alpha, rate_penalty=rate_penalty,
-                                drag=drag, wind_speed=wind_speed, gust_sigma=gust_sigma,
-                                gust_rate=gust_rate, reach_radius=reach_radius,
-                                reach_bonus=reach_bonus, mass_spread=mass_spread,
-                                inertia_spread=inertia_spread, motor_spread=motor_spread)
+                                **env_options)
         self.num_envs = num_envs
         od = self.batch.obs_dim
         self.single_observation_space = make_box(-np.inf, np.inf, (od,), np.float32)

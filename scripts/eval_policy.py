@@ -66,37 +66,36 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from drone_rl_amd import DroneBatch  # noqa: E402
-from drone_rl_amd.env import (HOVER, MOTOR_MAX, OBS_DIM, check_airframe, check_tag,  # noqa: E402
-                              check_waypoints, check_wind)
+from drone_rl_amd.env import ENV_OPTION, HOVER, MOTOR_MAX, OBS_DIM, check_tag  # noqa: E402
 from drone_rl_amd.policy import ActorCritic, PolicyInference  # noqa: E402
 
 
-WIND_KEYS = ("drag", "wind_speed", "gust_sigma", "gust_rate")
+WIND, COURSE, AIRFRAME = ENV_OPTION["wind"], ENV_OPTION["waypoints"], ENV_OPTION["airframe"]
+# the help of each gym option's flags here (one text for all of an option's
+# flags, or one per flag)
+HELP = {
+    WIND: ("gym checkpoints: evaluate under this wind parameter (default: the checkpoint's)",) * 4,
+    COURSE: ("gym checkpoints: fly waypoint courses with this reach radius "
+             "(default: the checkpoint's; 0 = the plain gym env)",
+             "gym checkpoints: the reward added in the step of a reach"),
+    AIRFRAME: ("gym checkpoints: fly on airframes drawn with this spread "
+               "(default: the checkpoint's)",) * 3,
+}
 
 
-def wind_of(cfg, args):
-    """The four wind values: the command line's, else the checkpoint's."""
-    return tuple(float(cfg.get(k, 0.0)) if getattr(args, k) is None else getattr(args, k)
-                 for k in WIND_KEYS)
-
-
-AIRFRAME_KEYS = ("mass_spread", "inertia_spread", "motor_spread")
-
-
-def airframe_of(cfg, args):
-    """The three spreads: the command line's, else the checkpoint's."""
-    return tuple(float(cfg.get(k, 0.0)) if getattr(args, k) is None else getattr(args, k)
-                 for k in AIRFRAME_KEYS)
+def values_of(option, cfg, args):
+    """An option's values, per keyword the command line's, else the
+    checkpoint's (its off value for checkpoints from before the option)."""
+    return tuple(cfg.get(k, d) if getattr(args, k) is None else getattr(args, k)
+                 for k, d in zip(option.keys, option.defaults))
 
 
 def course_of(cfg, args):
-    """(reach_radius, reach_bonus) or (None, None): the command line's values,
-    else the checkpoint's; --reach-radius 0 switches the option off."""
-    r = cfg.get("reach_radius") if args.reach_radius is None else args.reach_radius
-    b = cfg.get("reach_bonus") if args.reach_bonus is None else args.reach_bonus
+    """(reach_radius, reach_bonus) or (None, None): values_of the course, but
+    --reach-radius 0 switches the option off."""
     if args.reach_radius is not None and args.reach_radius == 0:
         return None, None
-    return r, b
+    return values_of(COURSE, cfg, args)
 
 
 def frozen_normaliser(sd, envs, obs_dim, dev, normalize=True):
@@ -130,9 +129,8 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     pol = ActorCritic(OBS_DIM[variant], 4, tuple(cfg["net_arch"]), dev, 0.0, 0)
     pol.flat.data.copy_(sd["flat"].to(dev))
     env = DroneBatch(envs, variant, device=dev, seed=seed, env_id_offset=1 << 40, monitor=True,
-                     motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND_KEYS, wind)),
-                     reach_radius=course[0], reach_bonus=course[1],
-                     **dict(zip(AIRFRAME_KEYS, airframe)))
+                     motor_alpha=alpha, rate_penalty=lam, **dict(zip(WIND.keys, wind)),
+                     **dict(zip(COURSE.keys, course)), **dict(zip(AIRFRAME.keys, airframe)))
     fixed = None
     if fixed_airframe is not None:
         # one airframe for every env and episode: the option enabled, its
@@ -247,19 +245,9 @@ def main():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--seed", type=int, default=123)
-    for k in WIND_KEYS:
-        ap.add_argument("--" + k.replace("_", "-"), type=float, default=None,
-                        help="gym checkpoints: evaluate under this wind parameter "
-                             "(default: the checkpoint's)")
-    ap.add_argument("--reach-radius", type=float, default=None,
-                    help="gym checkpoints: fly waypoint courses with this reach radius "
-                         "(default: the checkpoint's; 0 = the plain gym env)")
-    ap.add_argument("--reach-bonus", type=float, default=None,
-                    help="gym checkpoints: the reward added in the step of a reach")
-    for k in AIRFRAME_KEYS:
-        ap.add_argument("--" + k.replace("_", "-"), type=float, default=None,
-                        help="gym checkpoints: fly on airframes drawn with this spread "
-                             "(default: the checkpoint's)")
+    for option, texts in HELP.items():
+        for k, text in zip(option.keys, texts):
+            ap.add_argument("--" + k.replace("_", "-"), type=float, default=None, help=text)
     ap.add_argument("--fixed-airframe", default=None,
                     help="gym checkpoints: m,s,g0,g1,g2,g3 -- fly every episode on this one "
                          "airframe (not together with the spreads)")
@@ -279,31 +267,31 @@ def main():
     if out["variant"] == "tag":
         out["tag_radius"], out["crash_penalty"] = check_tag("tag", cfg.get("tag_radius"),
                                                             cfg.get("crash_penalty"))
-    wind = wind_of(cfg, a)
+    wind = values_of(WIND, cfg, a)
     if any(wind) or out["variant"] == "gym":
         # raises for a non-gym checkpoint with a wind flag
-        out.update(zip(WIND_KEYS, check_wind(out["variant"], *wind)))
+        out.update(zip(WIND.keys, WIND.check(out["variant"], *wind)))
     course = course_of(cfg, a)
     # raises for a non-gym checkpoint with a course flag, or wind and a course
-    rb = check_waypoints(out["variant"], *course, wind=wind)
+    rb = COURSE.check(out["variant"], *course, wind=wind)
     if rb is not None:
-        out["reach_radius"], out["reach_bonus"] = rb
+        out.update(zip(COURSE.keys, rb))
     fixed = None
     if a.fixed_airframe is not None:
         fixed = [float(x) for x in a.fixed_airframe.split(",")]
         if len(fixed) != 6 or not (0 < fixed[0] < float("inf") and 0 < fixed[1] < float("inf")):
             ap.error("--fixed-airframe takes m,s,g0,g1,g2,g3 with m, s positive and finite")
-        if any(getattr(a, k) for k in AIRFRAME_KEYS):
+        if any(getattr(a, k) for k in AIRFRAME.keys):
             ap.error("--fixed-airframe and the spreads exclude each other")
-    airframe = (0.0, 0.0, 0.0) if fixed is not None else airframe_of(cfg, a)
+    airframe = AIRFRAME.defaults if fixed is not None else values_of(AIRFRAME, cfg, a)
     if any(airframe) or fixed is not None or out["variant"] == "gym":
         # raises for a non-gym checkpoint with a spread, or a spread beside
         # wind or a course
-        out.update(zip(AIRFRAME_KEYS,
-                       check_airframe(out["variant"], *(airframe if fixed is None else (0.5,) * 3),
+        out.update(zip(AIRFRAME.keys,
+                       AIRFRAME.check(out["variant"], *(airframe if fixed is None else (0.5,) * 3),
                                       wind=wind, waypoints=rb)))
         if fixed is not None:
-            out.update(zip(AIRFRAME_KEYS, (0.0, 0.0, 0.0)))
+            out.update(zip(AIRFRAME.keys, AIRFRAME.defaults))
             out["fixed_airframe"] = fixed
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (

@@ -286,3 +286,59 @@ def test_rollout_and_first_epoch_share_one_gemm_path(num_envs):
                    "approx_kl"), tr.train().tolist()))
     assert st["approx_kl"] == 0.0 and st["clip_fraction"] == 0.0, st
     tr.close()
+
+
+def _small(**kw):
+    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
+    return PPOTrainer(PPOConfig(num_envs=64, n_steps=4, batch_size=256, n_epochs=1,
+                                net_arch=(64, 64), seed=5, **kw))
+
+
+# one set of values that switches each gym option of the env's table on
+_ON = {"wind": dict(drag=0.5, wind_speed=2.0, gust_sigma=0.5, gust_rate=0.125),
+       "waypoints": dict(reach_radius=0.5, reach_bonus=2.0),
+       "airframe": dict(mass_spread=0.25, inertia_spread=0.25, motor_spread=0.125)}
+
+
+def test_every_field_option_has_a_checkpoint_case():
+    from drone_rl_amd.env import ENV_OPTIONS
+    assert set(_ON) == {o.name for o in ENV_OPTIONS if o.field is not None}
+
+
+@pytest.mark.parametrize("name", sorted(_ON))
+def test_checkpoint_enables_the_option_it_carries(name, tmp_path):
+    """A checkpoint of a trainer with an option on, loaded into a trainer built
+    without it: the env takes the option with the checkpoint's values and
+    the field's contents (values exact in f32, so read back as given)."""
+    from drone_rl_amd.env import ENV_OPTION
+    o = ENV_OPTION[name]
+    a, b = _small(**_ON[name]), _small()
+    a.learn_step()
+    path = tmp_path / "ck.pt"
+    a.save(path)
+    assert a._env_fields()[-1] == o.field and o.field not in b._env_fields()
+    assert tuple(getattr(b.env, k) for k in o.keys) == o.idle
+    b.load(path)
+    assert getattr(b.env, name + "_enabled") and b._env_fields() == a._env_fields()
+    assert tuple(getattr(b.env, k) for k in o.keys) == tuple(_ON[name][k] for k in o.keys)
+    saved = torch.load(path, weights_only=True)["env"][o.field].to("cuda")
+    assert torch.equal(b.env.get(o.field), saved) and torch.equal(a.env.get(o.field), saved)
+    a.close()
+    b.close()
+
+
+def test_rollout_graph_is_dropped_after_set_wind():
+    """A new drag between two rollouts changes the rollout graph's key, and
+    the next rollout drops the captured graph for one with the new value."""
+    tr = _small(drag=0.5)
+    assert tr.rollout_graph
+    tr.collect_rollouts()
+    tr.collect_rollouts()
+    g0, k0 = tr._rgraph, tr._graph_key("rollout")
+    assert g0 is not None and tr._rkey == k0
+    tr.env.set_wind(drag=0.75)
+    k1 = tr._graph_key("rollout")
+    assert k1 != k0 and 0.5 in k0 and 0.75 in k1 and 0.5 not in k1
+    tr.collect_rollouts()
+    assert tr._rkey == k1 and tr._rgraph is not g0
+    tr.close()
