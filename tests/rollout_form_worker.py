@@ -10,6 +10,7 @@ import sys
 import torch
 
 from drone_rl_amd import DroneBatch, random_actions
+from rollout_parity import BASE, compare
 
 
 def main():
@@ -28,22 +29,14 @@ def main():
             s = x.get("current_step").cpu()
             s[::3] = max_steps - 2
             x.set("current_step", s)
-    step0 = 500 if max_steps else 0
-    acts = torch.empty(K, n, 4, device="cuda")
-    for t in range(K):
-        random_actions(n, seed=3, step=step0 + t, env_id_offset=5, out=acts[t])
+    fields = BASE + (("motion",) if variant == "moving" else ())
     if max_steps:
-        got = torch.empty(K, n, 4, device="cuda")
-        obs, rew, done = a.rollout(K, None, seed=3, step0=step0, actions_out=got)
-        assert torch.equal(got, acts)
+        obs, rew, done = compare(a, b, K, random=(3, 500), split=(K,), fields=fields)
     else:
-        obs, rew, done = a.rollout(K, acts)
-    for t in range(K):
-        so, sr, sd = b.step(acts[t])
-        assert torch.equal(obs[t], so) and torch.equal(rew[t], sr) and torch.equal(done[t], sd), t
-    fields = ("pos", "vel", "euler", "omega", "target", "current_step", "ep_num", "eps")
-    for k in fields + (("motion",) if variant == "moving" else ()):
-        assert torch.equal(a.get(k), b.get(k)), k
+        acts = torch.empty(K, n, 4, device="cuda")
+        for t in range(K):
+            random_actions(n, seed=3, step=t, env_id_offset=5, out=acts[t])
+        obs, rew, done = compare(a, b, K, actions=acts, split=(K,), fields=fields)
     assert int(done.sum()) >= (3 * n if max_steps else n // 8 + 1)
     print("ok", variant, n, K)
 

@@ -12,18 +12,7 @@ import pytest
 
 import airframe_ref
 from oracle import cref, drone_np
-
-
-def _state(g):
-    s = {k: np.array(g[k], np.float64, order="C")
-         for k in ("pos", "vel", "euler", "omega", "target")}
-    s["step"] = np.array(g["step"], np.int32)
-    return s
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
+from shared import bits as _bits, gym_state as _state
 
 
 # ---- ids and tables ---------------------------------------------------------

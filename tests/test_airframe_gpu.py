@@ -10,30 +10,22 @@ option's three changes, on random states.  Bars as for the gym env: done exact
 (f64), obs within 1e-5 * max(|ref|, 1), reward atol 2e-5; the airframe is
 exact f32 and compared bitwise.  Then every layer above the step kernel:
 resets, dr_rollout, the trainer with checkpoints, and the VecEnv facades."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import airframe_ref
+from rollout_parity import check_rollout, check_rollout_random
+from shared import f32_bits as _bits, gym_batch as _batch
+from subproc import run_worker
+from trainer_checks import (graph_equals_eager_and_resumes, graph_key_changes, plain_trainer,
+                            small_trainer)
 
 pytestmark = pytest.mark.gpu
 VEC = ("pos", "vel", "euler", "omega", "target")
 AIRFRAME = dict(mass_spread=0.3, inertia_spread=0.3, motor_spread=0.1)
 SPREADS = (0.3, 0.3, 0.1)
 F = lambda x: float(np.float32(x))   # noqa: E731
-
-
-def _batch(n, **kw):
-    from drone_rl_amd import DroneBatch
-    return DroneBatch(n, "gym", **kw)
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -239,81 +231,49 @@ def test_rollout_is_bitwise_k_steps(dtype):
     two reciprocals in registers) against K dr_step launches: outputs and
     every state field, `airframe` included, with resets inside the launch
     (max_steps 16 < K)."""
-    from airframe_rollout_worker import check_rollout, check_rollout_random
-    check_rollout(777, 37, dtype)
-    check_rollout_random(777, 37, dtype)
+    check_rollout("airframe", 777, 37, dtype)
+    check_rollout_random("airframe", 777, 37, dtype)
 
 
 def test_rollout_ignores_the_warp_specialised_override():
     """DRONERL_ROLLOUT_WS=1 forces the warp-specialised rollout forms for a
     plain gym handle; an airframe handle has only the one-role kernel and must
     keep it (the override is read once per process, hence the subprocess)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS="1", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "airframe_rollout_worker.py"),
-                        "f64", "777", "37"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_parity.py", "airframe", "f64", "777", "37", DRONERL_ROLLOUT_WS="1")
 
 
 # ---- trainer, checkpoints, VecEnv ------------------------------------------
-def _trainer(**kw):
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    return PPOTrainer(PPOConfig(num_envs=2048, n_steps=16, batch_size=4096, n_epochs=2,
-                                net_arch=(64, 64), seed=5, **(kw or AIRFRAME)))
-
-
 def test_trainer_fused_graph_and_checkpoint(tmp_path):
     """The trainer stays on the fused path (the obs is the gym's 15 floats);
     the captured rollout graph is bitwise the eager rollout; a checkpoint
     carries the spreads and the field and resumes bit for bit."""
-    a, b = _trainer(), _trainer()
-    b.rollout_graph = False
-    assert a.use_fused and a.obs.shape[-1] == 15 and a.env.airframe_enabled
-    assert (a.env.mass_spread, a.env.inertia_spread, a.env.motor_spread) == \
-        (F(0.3), F(0.3), F(0.1))
-    path = tmp_path / "ck.pt"
-    for it in range(3):
-        if it == 2:
-            sd = a.state_dict()
-            assert "airframe" in sd["env"] and sd["env"]["airframe"].shape == (2048, 6)
-            assert sd["config"]["mass_spread"] == 0.3 and sd["config"]["motor_spread"] == 0.1
-            a.save(path)
-        sa, sb = a.learn_step(), b.learn_step()
-        assert torch.isfinite(sa).all() and torch.equal(sa, sb)
-        for name in ("obs", "actions", "rewards", "dones", "adv"):
-            assert torch.equal(getattr(a, name), getattr(b, name)), (it, name)
-    assert a._rgraph is not None and b._rgraph is None
-    assert torch.isfinite(a.policy.flat).all()
-    c = _trainer()
-    c.load(path)
-    assert torch.equal(c.env.get("airframe"),
-                       torch.load(path, weights_only=True)["env"]["airframe"].to("cuda"))
-    c.learn_step()
-    assert torch.equal(a.policy.flat.detach(), c.policy.flat.detach())
-    for k in ("pos", "airframe", "ep_num"):
-        assert torch.equal(a.env.get(k), c.env.get(k)), k
-    assert a.num_timesteps == c.num_timesteps
-    assert bool((a.env.get("airframe") != 1).all(dim=1).any())
-    for t in (a, b, c):
-        t.close()
+    def make():
+        t = small_trainer(**AIRFRAME)
+        assert t.use_fused and t.obs.shape[-1] == 15 and t.env.airframe_enabled
+        assert (t.env.mass_spread, t.env.inertia_spread, t.env.motor_spread) == \
+            (F(0.3), F(0.3), F(0.1))
+        return t
+
+    def at_save(sd):
+        assert sd["config"]["mass_spread"] == 0.3 and sd["config"]["motor_spread"] == 0.1
+
+    def after(a, b):
+        assert bool((a.env.get("airframe") != 1).all(dim=1).any())
+
+    graph_equals_eager_and_resumes(make, tmp_path, field="airframe", field_shape=(2048, 6),
+                                   resume_fields=("pos", "airframe", "ep_num"), at_save=at_save,
+                                   after=after)
 
 
 def test_graph_key_follows_set_airframe():
     """A changed spread drops the captured rollout graph's key; so does
     enabling."""
-    a = _trainer()
-    k0 = a._graph_key("rollout")
-    a.env.set_airframe(0.3, 0.3, 0.2)
-    assert a._graph_key("rollout") != k0
+    a = small_trainer(**AIRFRAME)
+    graph_key_changes(a, lambda env: env.set_airframe(0.3, 0.3, 0.2))
     a.close()
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    g = PPOTrainer(PPOConfig(num_envs=256, n_steps=4, batch_size=1024, n_epochs=1,
-                             net_arch=(64, 64), seed=5))
-    k1 = g._graph_key("rollout")
-    g.env.set_airframe(**AIRFRAME)     # enabling changes the kernels a graph would hold
-    assert g._graph_key("rollout") != k1
+    g = plain_trainer()
+    # enabling changes the kernels a graph would hold
+    graph_key_changes(g, lambda env: env.set_airframe(**AIRFRAME))
     g.close()
 
 

@@ -65,7 +65,6 @@ threshold), and in both dtypes equal to the reference's own predicate
 recomputed from the position the kernel stored."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -74,6 +73,7 @@ import torch
 import env_states as es
 from env_states_worker import (K, actions_for, assert_same_run, check_rollout,
                                check_rollout_random, fields, new_batch, same_bits, step_run)
+from subproc import run_worker
 
 pytestmark = pytest.mark.gpu
 VARIANTS = ("gym", "moving", "smooth", "tag", "vectorized")
@@ -522,10 +522,4 @@ def test_rollout_forced_form_bitwise(variant, dtype, ws):
     """The rollout form the size rule does not pick at this size
     (DRONERL_ROLLOUT_WS is read once per process, hence the subprocess), and
     with ws = 1 the in-kernel policy's warp-specialised gym kernel."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS=ws, PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "env_states_worker.py"),
-                        variant, dtype, ws], env=env, capture_output=True, text=True,
-                       timeout=120)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("env_states_worker.py", variant, dtype, ws, timeout=120, DRONERL_ROLLOUT_WS=ws)

@@ -11,15 +11,15 @@ are not compared (IEEE 754 leaves them to the implementation).  Then every
 layer above the step kernel: dr_rollout against K dr_step, state access,
 masked reset, sharding, the trainer with checkpoints, and the facades."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import rk4_ref
+from rollout_parity import check_rollout, check_rollout_random
+from subproc import run_worker
+from trainer_checks import graph_equals_eager_and_resumes, small_trainer
 
 pytestmark = pytest.mark.gpu
 DT = {torch.float64: np.float64, torch.float32: np.float32}
@@ -213,9 +213,8 @@ def test_rollout_is_bitwise_k_steps(dtype, n):
     """dr_rollout / dr_rollout_random (the one-role kernel, the 13 state words
     in registers) against K = 19 dr_step launches, Philox resets inside the
     launches (max_steps 7), over two back-to-back launches."""
-    from rk4_rollout_worker import check_rollout, check_rollout_random
-    check_rollout(n, 19, dtype)
-    check_rollout_random(n, 19, dtype)
+    check_rollout("rk4", n, 19, dtype)
+    check_rollout_random("rk4", n, 19, dtype)
 
 
 @pytest.mark.parametrize("override", [dict(DRONERL_ROLLOUT_WS="1"),
@@ -227,13 +226,7 @@ def test_rollout_under_launch_form_overrides(override):
     half-populated-wave, nontemporal-load instance (what large batches get);
     the rollout must still equal it bitwise.  The overrides are read once per
     process or handle, hence the subprocess."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=root, **override)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "rk4_rollout_worker.py"),
-                        "f64", "321", "19"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_parity.py", "rk4", "f64", "321", "19", **override)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -335,42 +328,21 @@ def test_sharded_equals_unsharded():
 
 
 # ---- trainer, checkpoints, facades ------------------------------------------
-def _trainer():
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    return PPOTrainer(PPOConfig(num_envs=256, n_steps=16, batch_size=1024, n_epochs=2,
-                                net_arch=(64, 64), seed=5, variant="rk4"))
-
-
 def test_trainer_graph_and_checkpoint(tmp_path):
     """The trainer at obs width 16: the captured rollout graph is bitwise the
     eager rollout; a checkpoint carries `quat` (not `euler`) and resumes bit
     for bit."""
-    a, b = _trainer(), _trainer()
-    b.rollout_graph = False
-    assert a.obs.shape[-1] == 16 and a.env.variant == "rk4"
-    path = tmp_path / "ck.pt"
-    for it in range(3):
-        if it == 2:
-            env = a.state_dict()["env"]
-            assert "quat" in env and "euler" not in env and env["quat"].shape == (256, 4)
-            a.save(path)
-        sa, sb = a.learn_step(), b.learn_step()
-        assert torch.isfinite(sa).all() and torch.equal(sa, sb)
-        for name in ("obs", "actions", "rewards", "dones", "adv"):
-            assert torch.equal(getattr(a, name), getattr(b, name)), (it, name)
-    assert a._rgraph is not None and b._rgraph is None
-    assert torch.isfinite(a.policy.flat).all()
-    c = _trainer()
-    c.load(path)
-    assert torch.equal(c.env.get("quat"), torch.load(path, weights_only=True)["env"]["quat"]
-                       .to("cuda"))
-    c.learn_step()
-    assert torch.equal(a.policy.flat.detach(), c.policy.flat.detach())
-    for k in ("pos", "quat", "omega", "ep_num"):
-        assert torch.equal(a.env.get(k), c.env.get(k)), k
-    assert a.num_timesteps == c.num_timesteps
-    for t in (a, b, c):
-        t.close()
+    def make():
+        t = small_trainer(num_envs=256, batch_size=1024, variant="rk4")
+        assert t.obs.shape[-1] == 16 and t.env.variant == "rk4"
+        return t
+
+    def at_save(sd):
+        assert "euler" not in sd["env"]
+
+    graph_equals_eager_and_resumes(make, tmp_path, field="quat", field_shape=(256, 4),
+                                   resume_fields=("pos", "quat", "omega", "ep_num"),
+                                   at_save=at_save)
 
 
 def test_fused_step_matches_unfused_path_at_width_16():

@@ -15,6 +15,8 @@ import torch
 
 from drone_rl_amd import _lib
 from oracle import cref
+from rollout_parity import compare
+from subproc import run_worker
 
 pytestmark = pytest.mark.gpu
 
@@ -40,14 +42,9 @@ def _pair(n, variant, dtype, **kw):
     return a, b
 
 
-def _fields(b):
-    out = {k: b.get(k) for k in VEC + ("current_step",)}
-    if b.variant != "vectorized":
-        out["ep_num"] = b.get("ep_num")
-        out["eps"] = b.get("eps")
-    if b.variant == "moving":
-        out["motion"] = b.get("motion")
-    return out
+def _fields(variant):
+    return VEC + ("current_step",) + (("ep_num", "eps") if variant != "vectorized" else ()) + \
+        (("motion",) if variant == "moving" else ())
 
 
 @pytest.mark.parametrize("variant,dtype,n,max_steps", [
@@ -70,26 +67,14 @@ def test_rollout_is_bitwise_k_steps(variant, dtype, n, max_steps):
     for t in range(K):
         random_actions(n, seed=11, step=t, env_id_offset=3 * n, out=acts[t])
     # two launches back to back: the state carried across launch boundaries
-    o1, r1, d1 = a.rollout(K1, acts[:K1])
-    o2, r2, d2 = a.rollout(K2, acts[K1:])
-    obs = torch.cat([o1, o2])
-    rew = torch.cat([r1, r2])
-    done = torch.cat([d1, d2])
-    for t in range(K):
-        so, sr, sd = b.step(acts[t])
-        assert torch.equal(obs[t], so), (t, "obs")
-        assert torch.equal(rew[t], sr), (t, "rew")
-        assert torch.equal(done[t], sd), (t, "done")
-    fa, fb = _fields(a), _fields(b)
-    for k in fa:
-        assert torch.equal(fa[k], fb[k]), k
+    obs, rew, done = compare(a, b, K, actions=acts, split=(K1, K2), fields=_fields(variant))
     if variant != "vectorized":
         nd = int(done.sum())
         assert nd > n // 4, nd                  # resets happened in the launch
         if max_steps:
-            assert int(fa["current_step"].max()) < max_steps
+            assert int(a.get("current_step").max()) < max_steps
         # the curriculum bump (eps 0 -> 0.1) happened inside a launch
-        assert bool((fa["eps"][::7] == 0.1).any())
+        assert bool((a.get("eps")[::7] == 0.1).any())
 
 
 def test_rollout_random_policy_matches_random_actions():
@@ -124,7 +109,6 @@ def test_rollout_random_policy_small_ragged_with_resets(variant, dtype):
     third of the envs start at step 4, so they reset at t = 1 and t = 7, twice
     within one draw-ahead group: the drawn-ahead reset and the draw inside the
     reset branch both run, deterministically."""
-    from drone_rl_amd import random_actions
     n, K, seed, step0 = 321, 19, 2024, 700
     reset_variant = variant != "vectorized"
     a, b = _pair(n, variant, dtype, max_steps=6 if reset_variant else None)
@@ -133,20 +117,7 @@ def test_rollout_random_policy_small_ragged_with_resets(variant, dtype):
             s = x.get("current_step").cpu()
             s[::3] = 4
             x.set("current_step", s)
-    got = torch.empty(K, n, 4, device="cuda")
-    obs, rew, done = a.rollout(K, None, seed=seed, step0=step0, actions_out=got)
-    acts = torch.empty(K, n, 4, device="cuda")
-    for t in range(K):
-        random_actions(n, seed=seed, step=step0 + t, env_id_offset=3 * n, out=acts[t])
-    assert torch.equal(got, acts)
-    for t in range(K):
-        so, sr, sd = b.step(acts[t])
-        assert torch.equal(obs[t], so), (t, "obs")
-        assert torch.equal(rew[t], sr), (t, "rew")
-        assert torch.equal(done[t], sd), (t, "done")
-    fa, fb = _fields(a), _fields(b)
-    for k in fa:
-        assert torch.equal(fa[k], fb[k]), k
+    obs, rew, done = compare(a, b, K, random=(seed, step0), split=(K,), fields=_fields(variant))
     if reset_variant:
         assert int(done.sum()) >= 3 * n
 
@@ -154,16 +125,7 @@ def test_rollout_random_policy_small_ragged_with_resets(variant, dtype):
 def test_rollout_random_policy_one_role_form_forced():
     """The same check for (moving, f64) on the one-role kernel, which the size
     rule does not pick at n = 321 (DRONERL_ROLLOUT_WS=0, in a subprocess)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS="0", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "rollout_form_worker.py"),
-                        "moving", "321", "19", "6"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_form_worker.py", "moving", "321", "19", "6", DRONERL_ROLLOUT_WS="0")
 
 
 def test_rollout_last_step_vs_oracle():
@@ -245,9 +207,8 @@ def test_rollout_timed_same_outputs_and_packet_events():
     assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
     ms = e0.elapsed_time(e1)
     assert 0.0 < ms <= wall_ms, (ms, wall_ms)
-    fa, fb = _fields(a), _fields(b)
-    for k in fa:
-        assert torch.equal(fa[k], fb[k]), k
+    for k in _fields("gym"):
+        assert torch.equal(a.get(k), b.get(k)), k
     # null events: a plain launch; the outputs again those of dr_rollout
     assert L.dr_rollout_timed(b.handle, K, acts.data_ptr(), o2.data_ptr(), r2.data_ptr(),
                               d2.data_ptr(), s.cuda_stream, None, None) == _lib.DR_OK
@@ -265,13 +226,4 @@ def test_rollout_forms_outside_their_default(ws, variant, n):
     """Both kernel forms of dr_rollout stay bitwise equal to K dr_step launches
     in the regimes the size rule does not pick them for (DRONERL_ROLLOUT_WS
     forces a form; it is read once per process, hence the subprocess)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS=ws, PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "rollout_form_worker.py"),
-                        variant, str(n), "37"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_form_worker.py", variant, str(n), "37", DRONERL_ROLLOUT_WS=ws)

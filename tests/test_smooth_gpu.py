@@ -10,15 +10,14 @@ moving envs: done exact (f64), obs within 1e-5 * max(|ref|, 1), reward atol
 2e-5; the motor forces are exact f32 and compared bitwise.  Then every layer
 above the step kernel: auto-reset, dr_rollout, the K = 19 first-layer PPO
 kernels, the trainer with checkpoints, and the VecEnv facade."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+from rollout_parity import check_rollout, check_rollout_random
 from smooth_ref import HOVER, smooth_step
+from subproc import run_worker
+from trainer_checks import graph_equals_eager_and_resumes, graph_key_changes, small_trainer
 
 pytestmark = pytest.mark.gpu
 VEC = ("pos", "vel", "euler", "omega", "target")
@@ -145,22 +144,15 @@ def test_rollout_is_bitwise_k_steps(dtype):
     """dr_rollout / dr_rollout_random (the one-role kernel, the lag state in
     registers) against K dr_step launches: outputs and every state field,
     `motor` included, with resets inside the launch (max_steps 16 < K)."""
-    from smooth_rollout_worker import check_rollout, check_rollout_random
-    check_rollout(777, 37, dtype)
-    check_rollout_random(777, 37, dtype)
+    check_rollout("smooth", 777, 37, dtype)
+    check_rollout_random("smooth", 777, 37, dtype)
 
 
 def test_rollout_ignores_the_warp_specialised_override():
     """DRONERL_ROLLOUT_WS=1 forces the warp-specialised rollout forms for the
     other variants; this one has only the one-role kernel and must keep it
     (the override is read once per process, hence the subprocess)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS="1", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "smooth_rollout_worker.py"),
-                        "f64", "777", "37"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_parity.py", "smooth", "f64", "777", "37", DRONERL_ROLLOUT_WS="1")
 
 
 # ---- the first-layer PPO kernels at the 19-d observation -------------------
@@ -235,10 +227,7 @@ def test_fused_step_matches_unfused_path_at_width_19():
 
 # ---- trainer, checkpoints, VecEnv ------------------------------------------
 def _trainer():
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    return PPOTrainer(PPOConfig(num_envs=2048, n_steps=16, batch_size=4096, n_epochs=2,
-                                net_arch=(64, 64), seed=5, variant="smooth", motor_alpha=0.5,
-                                rate_penalty=0.01))
+    return small_trainer(variant="smooth", motor_alpha=0.5, rate_penalty=0.01)
 
 
 def test_trainer_fused_graph_and_checkpoint(tmp_path):
@@ -246,41 +235,21 @@ def test_trainer_fused_graph_and_checkpoint(tmp_path):
     rollout graph is bitwise the eager rollout (rollout_graph = False, what
     DRONERL_ROLLOUT_GRAPH=0 sets); a checkpoint carries the motor forces and
     resumes bit for bit."""
-    a, b = _trainer(), _trainer()
-    b.rollout_graph = False
-    assert a.use_fused and a.obs.shape[-1] == 19
-    assert (a.env.motor_alpha, a.env.rate_penalty) == (0.5, 0.01)
-    assert a._graph_key("rollout")[-2:] == (0.5, 0.01)
-    path = tmp_path / "ck.pt"
-    for it in range(3):
-        if it == 2:
-            assert "motor" in a.state_dict()["env"]
-            a.save(path)
-        sa, sb = a.learn_step(), b.learn_step()
-        assert torch.isfinite(sa).all() and torch.equal(sa, sb)
-        for name in ("obs", "actions", "rewards", "dones", "adv"):
-            assert torch.equal(getattr(a, name), getattr(b, name)), (it, name)
-    assert a._rgraph is not None and b._rgraph is None
-    assert torch.isfinite(a.policy.flat).all()
-    c = _trainer()
-    c.load(path)
-    assert torch.equal(c.env.get("motor"), torch.load(path, weights_only=True)["env"]["motor"]
-                       .to("cuda"))
-    c.learn_step()
-    assert torch.equal(a.policy.flat.detach(), c.policy.flat.detach())
-    for k in ("pos", "motor", "ep_num"):
-        assert torch.equal(a.env.get(k), c.env.get(k)), k
-    assert a.num_timesteps == c.num_timesteps
-    for t in (a, b, c):
-        t.close()
+    def make():
+        t = _trainer()
+        assert t.use_fused and t.obs.shape[-1] == 19
+        assert (t.env.motor_alpha, t.env.rate_penalty) == (0.5, 0.01)
+        assert t._graph_key("rollout")[-2:] == (0.5, 0.01)
+        return t
+
+    graph_equals_eager_and_resumes(make, tmp_path, field="motor", field_shape=(2048, 4),
+                                   resume_fields=("pos", "motor", "ep_num"))
 
 
 def test_graph_key_follows_set_smoothing():
     """A changed parameter drops the captured rollout graph's key."""
     a = _trainer()
-    k0 = a._graph_key("rollout")
-    a.env.set_smoothing(0.25, 0.01)
-    assert a._graph_key("rollout") != k0
+    graph_key_changes(a, lambda env: env.set_smoothing(0.25, 0.01))
     a.close()
 
 

@@ -12,14 +12,13 @@ layer above the step kernel: the pair's common reset, dr_reset_masked,
 dr_rollout, the trainer with checkpoints, and the VecEnv facade.  The batch
 sizes leave the last wave partly filled: 1030 = 16 * 64 + 6."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from rollout_parity import check_rollout, check_rollout_random
+from subproc import run_worker
 from tag_ref import tag_random_state, tag_step
 
 pytestmark = pytest.mark.gpu
@@ -219,31 +218,23 @@ def test_rollout_is_bitwise_k_steps(dtype, n):
     """dr_rollout / dr_rollout_random (the one-role kernel, the exchanges in
     registers) against K = 24 dr_step launches: outputs and every state
     field, with the pairs' resets inside the launch (max_steps 7)."""
-    from tag_rollout_worker import check_rollout, check_rollout_random
-    check_rollout(n, 24, dtype)
-    check_rollout_random(n, 24, dtype)
+    check_rollout("tag", n, 24, dtype)
+    check_rollout_random("tag", n, 24, dtype)
 
 
 def test_rollout_vs_half_populated_step_waves(monkeypatch):
     """DRONERL_ROWS_PER_WAVE=32 (read by dr_create) puts 32 envs on a wave of
     the step kernel; the rollout keeps 64.  Same bits."""
-    from tag_rollout_worker import check_rollout
     monkeypatch.setenv("DRONERL_ROWS_PER_WAVE", "32")
-    check_rollout(N, 24, torch.float64)
-    check_rollout(2, 24, torch.float32)
+    check_rollout("tag", N, 24, torch.float64)
+    check_rollout("tag", 2, 24, torch.float32)
 
 
 def test_rollout_ignores_the_warp_specialised_override():
     """DRONERL_ROLLOUT_WS=1 forces the warp-specialised rollout forms for the
     other variants; this one has only the one-role kernel and must keep it
     (the override is read once per process, hence the subprocess)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS="1", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "tag_rollout_worker.py"),
-                        "f64", f"{N},2", "24"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_parity.py", "tag", "f64", f"{N},2", "24", DRONERL_ROLLOUT_WS="1")
 
 
 def test_set_tag_abi():

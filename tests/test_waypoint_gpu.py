@@ -11,24 +11,20 @@ oracle's gym step, on random states.  Bars as for the gym env: done exact
 are compared exactly.  Then every layer above the step kernel: resets,
 dr_rollout, the trainer with checkpoints, and the VecEnv facades.  Every test
 asserts a minimum number of reaches, so none passes with the feature idle."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import waypoint_ref
+from rollout_parity import check_rollout, check_rollout_random
+from shared import gym_batch as _batch
+from subproc import run_worker
+from trainer_checks import (graph_equals_eager_and_resumes, graph_key_changes, plain_trainer,
+                            small_trainer)
 
 pytestmark = pytest.mark.gpu
 VEC = ("pos", "vel", "euler", "omega", "target")
 STATE = VEC + ("current_step", "ep_num", "eps")
-
-
-def _batch(n, **kw):
-    from drone_rl_amd import DroneBatch
-    return DroneBatch(n, "gym", **kw)
 
 
 def _bits(t):
@@ -296,9 +292,8 @@ def test_rollout_is_bitwise_k_steps(dtype):
     and counter in registers) against K dr_step launches: outputs and every
     state field, `waypoint` included, with reaches and resets inside the
     launch (max_steps 16 < K)."""
-    from waypoint_rollout_worker import check_rollout, check_rollout_random
-    reaches, deep = check_rollout(777, 37, dtype)
-    reaches_random = check_rollout_random(777, 37, dtype)
+    reaches, deep = check_rollout("waypoint", 777, 37, dtype)
+    reaches_random, _ = check_rollout_random("waypoint", 777, 37, dtype)
     print(f"rollout ({dtype}): reaches {reaches} / {reaches_random} (in-kernel actions), "
           f"envs that held j >= 3: {deep}")
     assert reaches >= 2000 and reaches_random >= 2000
@@ -309,21 +304,12 @@ def test_rollout_ignores_the_warp_specialised_override():
     """DRONERL_ROLLOUT_WS=1 forces the warp-specialised rollout forms for a
     plain gym handle; a waypoint handle has only the one-role kernel and must
     keep it (the override is read once per process, hence the subprocess)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRONERL_ROLLOUT_WS="1", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, os.path.join(root, "tests", "waypoint_rollout_worker.py"),
-                        "f64", "777", "37"], env=env, capture_output=True, text=True,
-                       timeout=100)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok" in r.stdout
+    run_worker("rollout_parity.py", "waypoint", "f64", "777", "37", DRONERL_ROLLOUT_WS="1")
 
 
 # ---- trainer, checkpoints, VecEnv ------------------------------------------
-def _trainer(**kw):
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    kw = dict(dict(reach_radius=0.25, reach_bonus=1.0), **kw)
-    return PPOTrainer(PPOConfig(num_envs=2048, n_steps=16, batch_size=4096, n_epochs=2,
-                                net_arch=(64, 64), seed=5, **kw))
+def _trainer():
+    return small_trainer(reach_radius=0.25, reach_bonus=1.0)
 
 
 def test_trainer_fused_graph_and_checkpoint(tmp_path):
@@ -332,68 +318,51 @@ def test_trainer_fused_graph_and_checkpoint(tmp_path):
     carries the course parameters and field and resumes bit for bit, also into
     a trainer built without the option; episode_stats reports the waypoints
     per episode."""
-    a, b = _trainer(), _trainer()
-    b.rollout_graph = False
-    assert a.use_fused and a.obs.shape[-1] == 15 and a.env.waypoints_enabled
-    assert (a.env.reach_radius, a.env.reach_bonus) == (0.25, 1.0)
-    path = tmp_path / "ck.pt"
-    for it in range(3):
-        if it == 2:
-            sd = a.state_dict()
-            assert "waypoint" in sd["env"] and sd["env"]["waypoint"].shape == (2048, 2)
-            assert sd["env"]["waypoint"].dtype == torch.int32
-            assert sd["config"]["reach_radius"] == 0.25 and sd["config"]["reach_bonus"] == 1.0
-            a.save(path)
-        sa, sb = a.learn_step(), b.learn_step()
-        assert torch.isfinite(sa).all() and torch.equal(sa, sb)
-        for name in ("obs", "actions", "rewards", "dones", "adv"):
-            assert torch.equal(getattr(a, name), getattr(b, name)), (it, name)
-        ea, eb = a.episode_stats(), b.episode_stats()
-        assert ea == eb and np.isfinite(ea["ep_waypoints_mean"]) and ea["ep_waypoints_mean"] >= 0
-    assert a._rgraph is not None and b._rgraph is None
-    assert torch.isfinite(a.policy.flat).all()
-    # the reaches of the last rollout are what the counters gained in it
-    assert torch.equal(a.env.get("waypoint"), b.env.get("waypoint"))
-    assert int(a.env.get("waypoint")[:, 1].sum()) >= 16     # eps 0: starts within 0.25 m reach
-    saved = torch.load(path, weights_only=True)["env"]["waypoint"].to("cuda")
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    plain = PPOTrainer(PPOConfig(num_envs=2048, n_steps=16, batch_size=4096, n_epochs=2,
-                                 net_arch=(64, 64), seed=5))
-    assert not plain.env.waypoints_enabled
-    for c in (_trainer(), plain):
-        c.load(path)
-        assert c.env.waypoints_enabled
-        assert (c.env.reach_radius, c.env.reach_bonus) == (0.25, 1.0)
-        assert torch.equal(c.env.get("waypoint"), saved)
-        c.learn_step()
-        assert torch.equal(a.policy.flat.detach(), c.policy.flat.detach())
-        for k in ("pos", "target", "waypoint", "ep_num"):
-            assert torch.equal(a.env.get(k), c.env.get(k)), k
-        assert a.num_timesteps == c.num_timesteps
-        assert c.episode_stats() == a.episode_stats()
-        c.close()
-    for t in (a, b):
-        t.close()
+    def make():
+        t = _trainer()
+        assert t.use_fused and t.obs.shape[-1] == 15 and t.env.waypoints_enabled
+        assert (t.env.reach_radius, t.env.reach_bonus) == (0.25, 1.0)
+        return t
+
+    def plain():
+        t = small_trainer()
+        assert not t.env.waypoints_enabled
+        return t
+
+    def at_save(sd):
+        assert sd["env"]["waypoint"].dtype == torch.int32
+        assert sd["config"]["reach_radius"] == 0.25 and sd["config"]["reach_bonus"] == 1.0
+
+    def per_iter(a, x):
+        # x: the eager twin, or a trainer that loaded the checkpoint and stepped once
+        assert x.env.waypoints_enabled
+        assert (x.env.reach_radius, x.env.reach_bonus) == (0.25, 1.0)
+        ea, ex = a.episode_stats(), x.episode_stats()
+        assert ea == ex and np.isfinite(ea["ep_waypoints_mean"]) and ea["ep_waypoints_mean"] >= 0
+
+    def after(a, b):
+        # the reaches of the last rollout are what the counters gained in it
+        assert torch.equal(a.env.get("waypoint"), b.env.get("waypoint"))
+        assert int(a.env.get("waypoint")[:, 1].sum()) >= 16     # eps 0: starts within 0.25 m reach
+
+    graph_equals_eager_and_resumes(make, tmp_path, field="waypoint", field_shape=(2048, 2),
+                                   resume_fields=("pos", "target", "waypoint", "ep_num"),
+                                   at_save=at_save, per_iter=per_iter, after=after,
+                                   resume_into=(plain,))
 
 
 def test_graph_key_follows_set_waypoints():
     """A changed parameter drops the captured rollout graph's key; its last
     two entries stay the smoothing pair."""
     a = _trainer()
-    k0 = a._graph_key("rollout")
-    a.env.set_waypoints(0.5, 1.0)
-    k1 = a._graph_key("rollout")
-    assert k1 != k0 and k1[-2:] == k0[-2:] == (a.env.motor_alpha, a.env.rate_penalty)
-    a.env.set_waypoints(0.5, 2.0)
-    assert a._graph_key("rollout") != k1
+    k0, k1 = graph_key_changes(a, lambda env: env.set_waypoints(0.5, 1.0))
+    assert k1[-2:] == k0[-2:] == (a.env.motor_alpha, a.env.rate_penalty)
+    graph_key_changes(a, lambda env: env.set_waypoints(0.5, 2.0))
     a.close()
-    from drone_rl_amd.ppo import PPOConfig, PPOTrainer
-    g = PPOTrainer(PPOConfig(num_envs=256, n_steps=4, batch_size=1024, n_epochs=1,
-                             net_arch=(64, 64), seed=5))
-    k2 = g._graph_key("rollout")
+    g = plain_trainer()
     assert "ep_waypoints_mean" not in g.episode_stats()
-    g.env.set_waypoints()                  # enabling changes the kernels a graph would hold
-    assert g._graph_key("rollout") != k2
+    # enabling changes the kernels a graph would hold
+    graph_key_changes(g, lambda env: env.set_waypoints())
     assert (g.env.reach_radius, g.env.reach_bonus) == (0.25, 1.0)
     g.close()
 

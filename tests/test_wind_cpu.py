@@ -11,20 +11,9 @@ import pytest
 
 import wind_ref
 from oracle import cref
+from shared import bits as _bits, gym_state as _state
 
 NEUTRAL = dict(drag=0.0, wind_speed=0.0, gust_sigma=0.0, gust_rate=0.0)
-
-
-def _state(g):
-    s = {k: np.array(g[k], np.float64, order="C")
-         for k in ("pos", "vel", "euler", "omega", "target")}
-    s["step"] = np.array(g["step"], np.int32)
-    return s
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
 
 
 def test_neutral_restatement_is_the_gym_step_bitwise(golden):

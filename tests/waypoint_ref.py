@@ -6,20 +6,9 @@ draws through oracle.cref.philox_np."""
 import numpy as np
 
 from oracle import cref
+from philox_ref import blocks as _blocks
 
 TAG_WAYPOINT = 0x57000000
-
-
-def _blocks(seed, gids, ep, word):
-    """The Philox blocks of counters (ep, gid_lo, gid_hi, word) under key
-    `seed`; gids / ep / word scalars or (n,) arrays.  Returns (n,4) uint32."""
-    gids = np.atleast_1d(np.asarray(gids)).astype(np.uint64)
-    n = len(gids)
-    m32 = np.uint64(0xffffffff)
-    ep = np.broadcast_to(np.asarray(ep).astype(np.int64).astype(np.uint64) & m32, (n,))
-    word = np.broadcast_to(np.asarray(word).astype(np.int64).astype(np.uint64) & m32, (n,))
-    ctr = np.stack([ep, gids & m32, gids >> np.uint64(32), word], 1)
-    return cref.philox_np(ctr, [seed & 0xffffffff, (seed >> 32) & 0xffffffff])
 
 
 def waypoint(seed, gids, ep, j, eps):

@@ -8,28 +8,11 @@ import math
 import numpy as np
 
 from oracle import cref
+from philox_ref import blocks as _blocks, pm1 as _pm1
 
 DT = 0.02
 TAG_RESET = 0x52000000
 TAG_GUST = 0x47000000
-
-
-def _blocks(seed, gids, ep, word):
-    """The Philox blocks of counters (ep, gid_lo, gid_hi, word) under key
-    `seed`; gids / ep / word scalars or (n,) arrays.  Returns (n,4) uint32."""
-    gids = np.atleast_1d(np.asarray(gids)).astype(np.uint64)
-    n = len(gids)
-    m32 = np.uint64(0xffffffff)
-    ep = np.broadcast_to(np.asarray(ep).astype(np.int64).astype(np.uint64) & m32, (n,))
-    word = np.broadcast_to(np.asarray(word).astype(np.int64).astype(np.uint64) & m32, (n,))
-    ctr = np.stack([ep, gids & m32, gids >> np.uint64(32), word], 1)
-    return cref.philox_np(ctr, [seed & 0xffffffff, (seed >> 32) & 0xffffffff])
-
-
-def _pm1(words):
-    """f32(2u - 1) of the words' uniforms u = w * 2^-32 (exact in f64, then
-    the one rounding)."""
-    return (2.0 * (words.astype(np.float64) * 2.0 ** -32) - 1.0).astype(np.float32)
 
 
 def mean_wind(seed, gids, ep, wind_speed):
