@@ -67,6 +67,14 @@ class dr_grad_finish(ctypes.Structure):
                 ("head_direct", c_int64)]
 
 
+class dr_kl_gate(ctypes.Structure):
+    """include/dronerl.h dr_kl_gate (KL control of one optimizer step)."""
+    _fields_ = [("control", c_void_p), ("num_steps", c_int64), ("step", c_int64),
+                ("kl", c_void_p), ("sched", c_void_p), ("stop_kl", c_float),
+                ("adaptive", c_int32), ("kl_high", c_float), ("kl_low", c_float),
+                ("lr_min", c_float), ("lr_max", c_float)]
+
+
 class DroneRLError(RuntimeError):
     """A libdronerl entry point returned a negative status."""
 
@@ -156,6 +164,10 @@ SIGNATURES = {
     "dr_grad_finish_run": (c_int, [_P, _P, c_size_t, _P]),
     "dr_clip_adam_sched": (c_int, [c_int64, _P, _P, _P, _P, c_double, c_double, c_double,
                                    c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    "dr_clip_adam_kl": (c_int, [c_int64, _P, _P, _P, _P, c_double, c_double, c_double,
+                                c_float, _P, _P, _P, c_size_t, _P]),
+    "dr_grad_finish_clip_adam_kl": (c_int, [_P, c_int64, _P, _P, _P, _P, c_double, c_double,
+                                            c_double, c_float, _P, _P, _P, c_size_t, _P]),
     "dr_gemm_x6_weights_bytes": (c_size_t, [c_int64]),
     "dr_gemm_x6_split_weights": (c_int, [c_int64, _P, c_int, _P, _P]),
     "dr_gemm_x6": (c_int, [c_int64, c_int64, _P, _P, _P, _P]),

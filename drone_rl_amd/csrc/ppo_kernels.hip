@@ -2742,3 +2742,6 @@ int dr_first_layer_backward2(int64_t m, int64_t k, int64_t n, const float *x,
 
 // VecNormalize (dr_vecnorm_*): its own file, this translation unit.
 #include "vecnorm.hip"
+
+// KL control of the optimizer step (dr_*_clip_adam_kl): likewise.
+#include "kl_control.hip"

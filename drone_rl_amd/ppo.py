@@ -133,12 +133,30 @@ class PPOConfig:
     clip_obs: float = 10.0
     clip_reward: float = 10.0
     norm_epsilon: float = 1e-8
+    # KL control of the optimizer steps, all off by
+    # default.  target_kl: SB3's early stop -- once a minibatch's approx_kl
+    # exceeds 1.5 * target_kl the rest of the iteration's steps, that one
+    # included, are not applied.  lr_schedule: "constant", "linear" (SB3's
+    # linear schedule over learn()'s total_timesteps) or "adaptive" (the rate
+    # moves by factors of 1.5 inside [lr_min, lr_max] to hold approx_kl near
+    # desired_kl).  Both are decided on the device by the kernel that applies
+    # Adam.  One GPU only (ranks would see different KLs)
+    target_kl: float | None = None
+    lr_schedule: str = "constant"
+    desired_kl: float = 0.01
+    lr_min: float = 1e-6
+    lr_max: float = 1e-2
 
     def __post_init__(self):
         if self.variant not in OBS_DIM:
             raise ValueError(f"unknown variant {self.variant!r}")
         check_env_options(self.variant, self.env_options(), num_envs=self.num_envs)
         K.check_vecnorm(self.clip_obs, self.clip_reward, self.norm_epsilon, self.gamma)
+        K.check_kl_control(self.target_kl, self.lr_schedule, self.desired_kl, self.lr_min,
+                           self.lr_max)
+
+    def kl_control_on(self) -> bool:
+        return self.target_kl is not None or self.lr_schedule != "constant"
 
     def env_options(self) -> dict:
         """The env's option keywords (env.ENV_OPTIONS) as DroneBatch takes them."""
@@ -155,6 +173,9 @@ class PPOConfig:
 
 
 class PPOTrainer:
+    _KL_DP_REFUSAL = ("target_kl / lr_schedule need world_size 1 and the single-GPU step: the "
+                      "ranks would see different KLs and diverge")
+
     def __init__(self, cfg: PPOConfig, device=None, rank: int = 0, world_size: int = 1,
                  process_group=None):
         self.cfg = cfg
@@ -163,6 +184,8 @@ class PPOTrainer:
         if world_size > 1 and (cfg.normalize_obs or cfg.normalize_reward):
             raise ValueError("normalize_obs / normalize_reward need world_size 1: the running "
                              "statistics are not merged across ranks")
+        if cfg.kl_control_on() and (world_size > 1 or cfg.force_dp_path):
+            raise ValueError(self._KL_DP_REFUSAL)
         self.device = torch.device("cuda", torch.cuda.current_device()) \
             if device is None else torch.device(device)
         N, T = cfg.num_envs, cfg.n_steps
@@ -274,9 +297,106 @@ class PPOTrainer:
         if cfg.normalize_obs or cfg.normalize_reward:
             self._enable_vecnorm(cfg.normalize_obs, cfg.normalize_reward, cfg.clip_obs,
                                  cfg.clip_reward, cfg.norm_epsilon)
+        # KL control (off: nothing allocated, the launches of before)
+        self._kl, self.stop_kl = None, None
+        self._kl_host, self._kl_event = None, None
+        self._total_timesteps = None
+        self._last_stats, self._last_taken = None, 0
+        if cfg.kl_control_on():
+            self._enable_kl(cfg.target_kl, cfg.lr_schedule, cfg.desired_kl, cfg.lr_min,
+                            cfg.lr_max)
         self._reset_env()
         if self.world > 1:
             self.sync_params()
+
+    # ------------------------------------------------------------- KL control
+    def _opt_steps(self) -> int:
+        c = self.cfg
+        return c.n_epochs * (c.n_steps * c.num_envs // c.batch_size)
+
+    def _enable_kl(self, target_kl, lr_schedule, desired_kl, lr_min, lr_max, lr=None):
+        """Turn the settings on: the control block (for target_kl and the
+        adaptive schedule; the linear one travels through the Adam table
+        alone) and the gated optimizer step in place of the plain one."""
+        if self.world > 1 or self.cfg.force_dp_path:
+            raise ValueError(self._KL_DP_REFUSAL)
+        K.check_kl_control(target_kl, lr_schedule, desired_kl, lr_min, lr_max)
+        self.opt.t                  # settle a count still owed by the old control block
+        if lr is None and self._kl is not None and self._kl.adaptive:
+            lr = self.kl_state()["lr"]              # an adaptive rate carries over
+        self.cfg = dataclasses.replace(
+            self.cfg, target_kl=None if target_kl is None else float(target_kl),
+            lr_schedule=lr_schedule, desired_kl=float(desired_kl), lr_min=float(lr_min),
+            lr_max=float(lr_max))
+        self._kl, self.stop_kl = None, None
+        adaptive = lr_schedule == "adaptive"
+        if target_kl is not None or adaptive:
+            self._kl = K.KLControl(self._opt_steps(), self.device, target_kl, adaptive,
+                                   desired_kl, lr_min, lr_max,
+                                   lr=self.opt.lr if lr is None else lr)
+            if target_kl is not None:
+                self.stop_kl = self._kl.stop_kl
+                self._kl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self._tgraph = None
+
+    def _kl_begin_host(self):
+        """Before an iteration's steps are enqueued: the Adam table for steps
+        t0 + 1 .. t0 + S (at lr 1 when the rate is the control block's) and
+        slot 0's rate.  Reading opt.t settles the steps the iteration before
+        took, which waits for work enqueued an iteration ago."""
+        S, kl = self._opt_steps(), self._kl
+        if getattr(self, "_sched", None) is None:
+            self._sched = torch.zeros(S, 2, dtype=torch.float32, device=self.device)
+        t0 = self.opt.t
+        self.opt.schedule(t0 + 1, S, out=self._sched, lr=1.0 if kl.adaptive else None)
+        if not kl.adaptive:
+            kl.set_lr(self.opt.lr)
+        return t0
+
+    def _kl_end_host(self, t0):
+        """After they are enqueued: without a target every step is taken; with
+        one the count comes back through pinned memory, read when opt.t is."""
+        S, kl = self._opt_steps(), self._kl
+        if kl.target_kl is None:
+            self.opt.t = t0 + S
+            self._last_taken = S
+            return
+        self._kl_host.copy_(kl.final(), non_blocking=True)
+        self._kl_event = torch.cuda.Event()
+        self._kl_event.record(torch.cuda.current_stream(self.device))
+        self._last_taken = None
+        self.opt.defer_steps(self._kl_taken)
+
+    def _kl_taken(self) -> int:
+        self._kl_event.synchronize()
+        self._last_taken = int(self._kl_host[0])
+        return self._last_taken
+
+    def _kl_mean(self, stats):
+        """Mean of the stats rows up to the stop, the tripping step included,
+        on the device; every row when nothing stopped."""
+        kl = self._kl
+        if kl is None or kl.target_kl is None:
+            return stats.mean(0)
+        w = kl.applied_mask()
+        part = torch.where(w[:, None], stats, 0.0).sum(0) / w.sum()
+        return torch.where(w.all(), stats.mean(0), part)
+
+    @property
+    def train_stats(self):
+        """(S, 8) per-step stats rows of the last train()."""
+        return self._last_stats
+
+    def kl_state(self) -> dict:
+        """n_updates_taken: the optimizer steps the last train() applied; lr:
+        the rate of its last applied step (reads back when on the device)."""
+        self.opt.t                          # settles _last_taken
+        kl = self._kl
+        if kl is not None and kl.adaptive:
+            lr = float(kl.slots.view(torch.float32)[kl.steps, 2].item())
+        else:
+            lr = float(self.opt.lr)
+        return {"n_updates_taken": int(self._last_taken), "lr": lr}
 
     # ----------------------------------------------------------- VecNormalize
     def _enable_vecnorm(self, norm_obs, norm_reward, clip_obs, clip_reward, epsilon):
@@ -424,11 +544,17 @@ class PPOTrainer:
                 tuple(x for o in reversed(self.env.option_state()) for x in o) + \
                 (() if self.vecnorm is None else
                  (v.flags(), v.gamma, v.clip_obs, v.clip_reward, v.epsilon))
-        o = self.opt
+        o, kl = self.opt, self._kl
+        # "linear" and "adaptive": the rate is device data (the Adam table,
+        # the control block), so the key carries the mode, not the value
+        lr = float(o.lr) if c.lr_schedule == "constant" else \
+            (c.lr_schedule, c.desired_kl, c.lr_min, c.lr_max)
         return (c.seed, self.rank, c.n_epochs, c.batch_size, c.clip_range, c.ent_coef,
-                c.vf_coef, c.normalize_advantage, float(o.lr), o.b1, o.b2, o.eps,
+                c.vf_coef, c.normalize_advantage, lr, o.b1, o.b2, o.eps,
                 o.max_norm, float(self.head.clip), float(self.head.ent), float(self.head.vf),
-                self.head.norm)
+                self.head.norm) + \
+            (() if kl is None else
+             (kl.stop_kl, kl.adaptive, kl.kl_high, kl.kl_low, kl.lr_min, kl.lr_max))
 
     def _train_fast(self) -> bool:
         """The deferred-finish step with device-side Adam scalars: the
@@ -449,6 +575,8 @@ class PPOTrainer:
         bias-correction schedule): the same kernels and numerics as train(),
         capturable into one hipGraph."""
         cfg, M = self.cfg, self.cfg.batch_size
+        if self._kl is not None:
+            self._kl.begin()
         if self.overlap_gather:
             return self._train_body_overlap(obs_flat, act_flat, nmb)
         j = 0
@@ -473,7 +601,11 @@ class PPOTrainer:
         in self.head.adv_part)."""
         grad, _ = self.fused.step(mb_obs, mb_act, mb_aux, self.head, adv_ready=True,
                                   stats_out=self._tstats[j], defer_finish=True)
-        if self.dp_step:
+        if self._kl is not None:
+            # the gate reads this step's approx_kl where the finish leaves it
+            self.opt.step_finish_kl(grad, self.fused.finish, self._kl, j, self._tstats[j, 5:6],
+                                    self._sched)
+        elif self.dp_step:
             # finish -> one all-reduce (sum) of the 564 KB flat gradient ->
             # clip+Adam on its mean (SURVEY.md 8e)
             self.fused.finish.run(self.device)
@@ -543,8 +675,12 @@ class PPOTrainer:
             self._sched = torch.zeros(S, 2, dtype=torch.float32, device=self.device)
             self._pctr = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._pctr.fill_(self.num_updates * cfg.n_epochs)
-        self.opt.schedule(self.opt.t + 1, S, out=self._sched)
-        self.opt.t += S
+        if self._kl is None:
+            self.opt.schedule(self.opt.t + 1, S, out=self._sched)
+            self.opt.t += S
+            self._last_taken = S
+        else:
+            t0 = self._kl_begin_host()
         obs_flat = self.obs[:T].reshape(T * N, -1)
         act_flat = self.actions.reshape(T * N, 4)
         key = self._graph_key("train")
@@ -568,8 +704,11 @@ class PPOTrainer:
             cur.wait_stream(cs)
             g.replay()
             self._tgraph = g
+        if self._kl is not None:
+            self._kl_end_host(t0)
         self.num_updates += 1
-        return self._tstats.mean(0)
+        self._last_stats = self._tstats
+        return self._kl_mean(self._tstats)
 
     @torch.no_grad()
     def train(self):
@@ -582,6 +721,11 @@ class PPOTrainer:
         log_std = self.policy.log_std.detach()
         nmb = T * N // M
         stats = torch.zeros(cfg.n_epochs * nmb, 8, dtype=torch.float32, device=self.device)
+        kl = self._kl
+        if kl is not None:
+            # the same gate as the fast path, launch by launch from the host
+            t0 = self._kl_begin_host()
+            kl.begin()
         j = 0
         for epoch in range(cfg.n_epochs):
             perm = self.perm(seed=cfg.seed * 104729 + self.rank,
@@ -611,7 +755,11 @@ class PPOTrainer:
                         # reductions and the norm in one launch before Adam
                         grad, st = self.fused.step(self.mb_obs, self.mb_act, self.mb_aux,
                                                    self.head, defer_finish=True, **kw)
-                        self.opt.step_finish(grad, self.fused.finish)
+                        if kl is not None:
+                            self.opt.step_finish_kl(grad, self.fused.finish, kl, j,
+                                                    stats[j, 5:6], self._sched)
+                        else:
+                            self.opt.step_finish(grad, self.fused.finish)
                         j += 1
                         continue
                     else:
@@ -626,12 +774,20 @@ class PPOTrainer:
                                                       aux=self.mb_aux)
                     grad = self.fused.backward(self.mb_obs, cache, g_mean, g_v, g_ls)
                     self._allreduce_grad(grad)
-                self.opt.step(grad)
+                if kl is not None:
+                    self.opt.step_kl(grad, kl, j, st[5:6], self._sched)
+                else:
+                    self.opt.step(grad)
                 if st.data_ptr() != stats[j].data_ptr():
                     stats[j].copy_(st)
                 j += 1
+        if kl is not None:
+            self._kl_end_host(t0)
+        else:
+            self._last_taken = j
         self.num_updates += 1
-        return stats.mean(0)
+        self._last_stats = stats
+        return self._kl_mean(stats)
 
     def learn_step(self):
         """One PPO iteration: rollout + GAE + n_epochs of minibatch updates."""
@@ -640,6 +796,10 @@ class PPOTrainer:
                 self.env.set("eps", torch.full((self.cfg.num_envs,), float(eps),
                                                dtype=torch.float64))
         self.collect_rollouts()
+        if self.cfg.lr_schedule == "linear" and self._total_timesteps:
+            # SB3's linear schedule: progress counts the rollout just collected
+            self.opt.lr = self.cfg.learning_rate * max(
+                0.0, 1.0 - self.num_timesteps / self._total_timesteps)
         return self.train()
 
     def episode_stats(self):
@@ -672,10 +832,12 @@ class PPOTrainer:
             out["ep_rew_mean_evader"] = s[5].item() / max(s[6].item(), 1.0)
         if wp:
             out["ep_waypoints_mean"] = s[-1].item() / n
+        out.update(self.kl_state())
         return out
 
     def learn(self, total_timesteps: int, log_every: int = 1, logger=print):
         t0 = time.perf_counter()
+        self._total_timesteps = int(total_timesteps)
         while self.num_timesteps < total_timesteps:
             st = self.learn_step()
             if logger and self.rank == 0 and self.num_updates % log_every == 0:
@@ -709,6 +871,11 @@ class PPOTrainer:
         T = self.cfg.n_steps
         # (last_obs is what the policy saw: normalised when the option is on)
         extra = {} if self.vecnorm is None else {"vecnorm": self.vecnorm.state_dict()}
+        if self.cfg.kl_control_on():
+            c = self.cfg
+            extra["kl_control"] = {"target_kl": c.target_kl, "lr_schedule": c.lr_schedule,
+                                   "desired_kl": c.desired_kl, "lr_min": c.lr_min,
+                                   "lr_max": c.lr_max, "lr": self.kl_state()["lr"]}
         return {
             **extra,
             "config": dataclasses.asdict(self.cfg),
@@ -749,6 +916,12 @@ class PPOTrainer:
                                          vs["clip_reward"], vs["epsilon"])
                 self.vecnorm.load_state_dict(vs)
                 self._rgraph = None
+            if "kl_control" in sd:
+                # likewise: the checkpoint's settings, and the rate an
+                # adaptive run had reached
+                ks = sd["kl_control"]
+                self._enable_kl(ks["target_kl"], ks["lr_schedule"], ks["desired_kl"],
+                                ks["lr_min"], ks["lr_max"], lr=ks["lr"])
             self.obs[0].copy_(sd["last_obs"].to(self.device))
             self.dones[T].copy_(sd["last_dones"].to(self.device))
         self._rolled = False

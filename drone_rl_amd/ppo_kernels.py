@@ -169,11 +169,64 @@ class ClipAdam:
         self.v = torch.zeros_like(params)
         self.lr, self.b1, self.b2, self.eps = lr, betas[0], betas[1], eps
         self.max_norm = max_grad_norm
-        self.t = 0
+        self._t, self._t_pending = 0, None
         n = params.numel()
         self.ws = torch.empty(_lib.lib().dr_adam_workspace_bytes(n), dtype=torch.uint8,
                               device=params.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=params.device)
+
+    @property
+    def t(self) -> int:
+        """Adam's step count.  Behind a KL gate the steps an iteration took
+        are known on the device only; the trainer leaves a callable that
+        fetches them, called here the first time the count is needed."""
+        if self._t_pending is not None:
+            fetch, self._t_pending = self._t_pending, None
+            self._t += int(fetch())
+        return self._t
+
+    @t.setter
+    def t(self, value: int):
+        self._t_pending = None
+        self._t = int(value)
+
+    def defer_steps(self, fetch):
+        """Advance t by fetch() when t is next read (see t)."""
+        self.t                      # settle an earlier one first
+        self._t_pending = fetch
+
+    def _finish_ws(self, finish: "GradFinish"):
+        f = ctypes.byref(finish.desc)
+        need = _lib.lib().dr_grad_finish_workspace_bytes(f)
+        if finish.ws is None or finish.ws.numel() < need:
+            finish.ws = torch.empty(need, dtype=torch.uint8, device=self.p.device)
+        return f
+
+    def step_kl(self, grads: torch.Tensor, ctl: "KLControl", j: int, kl: torch.Tensor,
+                sched: torch.Tensor):
+        """step_sched at grad_scale 1 behind the KL gate (dr_clip_adam_kl):
+        optimizer step j of ctl's iteration, `kl` this step's approx_kl (one
+        f32 on the device), `sched` the iteration's whole (steps, 2) table.
+        Graph-capturable; advances nothing on the host."""
+        g = ctl.gate(j, kl, sched)
+        check(_lib.lib().dr_clip_adam_kl(
+            self.p.numel(), ptr(self.p), ptr(_f32(grads)), ptr(self.m), ptr(self.v),
+            float(self.b1), float(self.b2), float(self.eps), float(self.max_norm),
+            ctypes.byref(g), ptr(self.grad_norm), ptr(self.ws), self.ws.numel(), _s(self.p)))
+        return self.grad_norm
+
+    def step_finish_kl(self, grads: torch.Tensor, finish: "GradFinish", ctl: "KLControl",
+                       j: int, kl: torch.Tensor, sched: torch.Tensor):
+        """step_finish_sched behind the KL gate (dr_grad_finish_clip_adam_kl);
+        arguments as step_kl."""
+        f = self._finish_ws(finish)
+        g = ctl.gate(j, kl, sched)
+        check(_lib.lib().dr_grad_finish_clip_adam_kl(
+            f, self.p.numel(), ptr(self.p), ptr(_f32(grads)), ptr(self.m), ptr(self.v),
+            float(self.b1), float(self.b2), float(self.eps), float(self.max_norm),
+            ctypes.byref(g), ptr(self.grad_norm), ptr(finish.ws), finish.ws.numel(),
+            _s(self.p)))
+        return self.grad_norm
 
     def step_finish(self, grads: torch.Tensor, finish: "GradFinish", lr=None):
         """step() for a gradient whose last reductions were deferred
@@ -192,13 +245,15 @@ class ClipAdam:
             ptr(finish.ws), finish.ws.numel(), _s(self.p)))
         return self.grad_norm
 
-    def schedule(self, first_step: int, count: int, out: torch.Tensor | None = None):
+    def schedule(self, first_step: int, count: int, out: torch.Tensor | None = None, lr=None):
         """(count, 2) f32 of Adam's step-dependent scalars for steps
-        first_step .. first_step + count - 1 (dr_adam_schedule, host)."""
+        first_step .. first_step + count - 1 (dr_adam_schedule, host), at
+        `lr` when given (the adaptive KL gate's table is built at 1)."""
         L = _lib.lib()
         buf = (ctypes.c_float * (2 * count))()
+        lr = self.lr if lr is None else lr
         for j in range(count):
-            check(L.dr_adam_schedule(float(self.lr), float(self.b1), float(self.b2),
+            check(L.dr_adam_schedule(float(lr), float(self.b1), float(self.b2),
                                      first_step + j, ctypes.byref(buf, 8 * j)))
         t = torch.frombuffer(bytearray(buf), dtype=torch.float32).view(count, 2)
         if out is None:
@@ -243,6 +298,100 @@ class ClipAdam:
             float(self.eps), float(self.max_norm), self.t, ptr(self.grad_norm),
             ptr(self.ws), self.ws.numel(), _s(self.p)))
         return self.grad_norm
+
+
+LR_SCHEDULES = ("constant", "linear", "adaptive")
+
+
+def _f32_round(x: float) -> float:
+    """x rounded to f32, as a Python float."""
+    import struct
+    try:
+        return struct.unpack("f", struct.pack("f", float(x)))[0]
+    except OverflowError:
+        return float("inf") if x > 0 else float("-inf")
+
+
+def check_kl_control(target_kl, lr_schedule, desired_kl, lr_min, lr_max):
+    """The value rules of the KL-control settings, raised as ValueError on the
+    host before any device work."""
+    import math
+
+    def positive(v):
+        return isinstance(v, (int, float)) and not isinstance(v, bool) and \
+            math.isfinite(v) and v > 0
+
+    if target_kl is not None:
+        if not positive(target_kl):
+            raise ValueError(f"target_kl must be None or > 0 and finite, got {target_kl!r}")
+        if 1.5 * target_kl > 3.0e38 or _f32_round(1.5 * target_kl) <= 0.0:
+            raise ValueError(f"target_kl: 1.5 * target_kl must fit f32, got {target_kl!r}")
+    if lr_schedule not in LR_SCHEDULES:
+        raise ValueError(f"unknown lr_schedule {lr_schedule!r}: one of {LR_SCHEDULES}")
+    if not positive(desired_kl) or _f32_round(desired_kl / 2) <= 0.0 or 2 * desired_kl > 3.0e38:
+        raise ValueError(f"desired_kl must be > 0 and finite, got {desired_kl!r}")
+    for name, v in (("lr_min", lr_min), ("lr_max", lr_max)):
+        if not positive(v) or _f32_round(v) <= 0.0 or v > 3.0e38:
+            raise ValueError(f"{name} must be > 0 and finite, got {v!r}")
+    if lr_min > lr_max:
+        raise ValueError(f"lr_min must be <= lr_max, got {lr_min!r} > {lr_max!r}")
+
+
+class KLControl:
+    """The control block of the KL gate (dr_kl_gate):
+    `steps` + 1 slots of (stopped u32, taken u32, lr f32, pad) on the device.
+    Optimizer step j of an iteration reads slot j and writes slot j + 1; slot
+    0 keeps stopped = taken = 0 and gets the iteration's learning rate --
+    from the host (set_lr), or with `adaptive` from the last slot of the
+    iteration before, copied on the device by begin() (capturable)."""
+
+    def __init__(self, steps: int, device, target_kl=None, adaptive=False, desired_kl=0.01,
+                 lr_min=1e-6, lr_max=1e-2, lr=3e-4):
+        check_kl_control(target_kl, "adaptive" if adaptive else "constant", desired_kl, lr_min,
+                         lr_max)
+        if steps < 1:
+            raise ValueError("KLControl needs steps >= 1")
+        self.steps, self.adaptive = int(steps), bool(adaptive)
+        self.target_kl = None if target_kl is None else float(target_kl)
+        # f32(1.5 * target_kl): the product in double, one rounding
+        self.stop_kl = 0.0 if target_kl is None else _f32_round(1.5 * target_kl)
+        self.desired_kl = float(desired_kl)
+        self.kl_high, self.kl_low = _f32_round(2 * desired_kl), _f32_round(desired_kl / 2)
+        self.lr_min, self.lr_max = _f32_round(lr_min), _f32_round(lr_max)
+        self.slots = torch.zeros(self.steps + 1, 4, dtype=torch.int32, device=device)
+        self._lr = self.slots.view(torch.float32)[:, 2]
+        self.set_lr(lr, carry=True)
+
+    def set_lr(self, lr: float, carry=False):
+        """Slot 0's learning rate from the host; with `carry` also the last
+        slot's, which an adaptive begin() copies into slot 0."""
+        self._lr[0].fill_(float(lr))
+        if carry:
+            self._lr[self.steps].fill_(float(lr))
+
+    def begin(self):
+        """Start of an iteration, on the device: adaptive carries the rate the
+        last iteration ended at."""
+        if self.adaptive:
+            self._lr[0:1].copy_(self._lr[self.steps:self.steps + 1])
+
+    def gate(self, j: int, kl: torch.Tensor, sched: torch.Tensor) -> "_lib.dr_kl_gate":
+        assert 0 <= j < self.steps and tuple(sched.shape) == (self.steps, 2)
+        assert kl.numel() == 1 and _f32(sched).device == kl.device == self.slots.device
+        assert kl.dtype == torch.float32
+        return _lib.dr_kl_gate(control=ptr(self.slots), num_steps=self.steps, step=j,
+                               kl=ptr(kl), sched=ptr(sched), stop_kl=self.stop_kl,
+                               adaptive=int(self.adaptive), kl_high=self.kl_high,
+                               kl_low=self.kl_low, lr_min=self.lr_min, lr_max=self.lr_max)
+
+    def applied_mask(self) -> torch.Tensor:
+        """(steps,) bool on the device: the steps that ran before the stop,
+        the tripping one included (slot j not yet stopped)."""
+        return self.slots[:self.steps, 0] == 0
+
+    def final(self) -> torch.Tensor:
+        """The last slot's (taken, lr) as two int32 words on the device."""
+        return self.slots[self.steps, 1:3]
 
 
 LINEAR_TANH_K = (4, 8, 12, 15, 16, 18, 19, 24, 32)

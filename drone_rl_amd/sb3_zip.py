@@ -185,6 +185,7 @@ def save(trainer, path):
                                 "differentiable": False, "fused": None,
                                 "params": list(range(len(order)))}]}
     od = pol.obs_dim
+    target_kl = getattr(cfg, "target_kl", None)
     data = {
         "policy_class": _ser("<class 'abc.ABCMeta'>",
                              _global_pickle("stable_baselines3.common.policies",
@@ -222,7 +223,7 @@ def save(trainer, path):
         "clip_range": float(cfg.clip_range),
         "clip_range_vf": None,
         "normalize_advantage": bool(cfg.normalize_advantage),
-        "target_kl": None,
+        "target_kl": None if target_kl is None else float(target_kl),
     }
     env = {k: trainer.env.get(k).cpu().numpy() for k in ("ep_num", "eps")}
 
@@ -331,6 +332,12 @@ def load_into(trainer, path, load_env_state=True):
                                     bool(vn.get("norm_reward", True)), float(vn["clip_obs"]),
                                     float(vn["clip_reward"]), float(vn["epsilon"]))
         trainer.vecnorm.load_npz_dict(vn)
+    tkl = ck["data"].get("target_kl")
+    if tkl is not None and hasattr(trainer, "_enable_kl") and trainer.cfg.target_kl is None:
+        # likewise a checkpoint with an early stop: the trainer takes it (the
+        # schedule settings stay the trainer's; SB3's zip holds no others)
+        c = trainer.cfg
+        trainer._enable_kl(float(tkl), c.lr_schedule, c.desired_kl, c.lr_min, c.lr_max)
     return ck
 
 

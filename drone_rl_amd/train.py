@@ -102,7 +102,38 @@ def build_parser():
                     help="bound of the normalised observations")
     ap.add_argument("--clip-reward", type=float, default=10.0,
                     help="bound of the normalised rewards")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="SB3 target_kl: stop an iteration's optimizer steps once a "
+                         "minibatch's approx_kl exceeds 1.5 x this (one GPU)")
+    ap.add_argument("--lr-schedule", choices=["constant", "linear", "adaptive"],
+                    default="constant",
+                    help="linear = --lr down to 0 over --total-steps; adaptive = the rate "
+                         "follows approx_kl towards --desired-kl by factors of 1.5 (one GPU)")
+    ap.add_argument("--desired-kl", type=float, default=0.01,
+                    help="the approx_kl --lr-schedule adaptive steers to")
+    ap.add_argument("--lr-min", type=float, default=1e-6,
+                    help="lower bound of the adaptive learning rate")
+    ap.add_argument("--lr-max", type=float, default=1e-2,
+                    help="upper bound of the adaptive learning rate")
     return ap
+
+
+def config_from_args(a) -> PPOConfig:
+    """The PPOConfig the parsed command line describes."""
+    common = dict(num_envs=a.envs, learning_rate=a.lr, ent_coef=a.ent_coef, seed=a.seed,
+                  grad_buckets=a.grad_buckets,
+                  state_dtype=a.state_dtype, variant=a.variant, initial_eps=a.initial_eps,
+                  bootstrap_timeouts=a.bootstrap_timeouts, **option_values(a),
+                  normalize_obs=a.normalize_obs, normalize_reward=a.normalize_reward,
+                  clip_obs=a.clip_obs, clip_reward=a.clip_reward,
+                  target_kl=a.target_kl, lr_schedule=a.lr_schedule, desired_kl=a.desired_kl,
+                  lr_min=a.lr_min, lr_max=a.lr_max,
+                  eps_schedule=tuple((int(u), float(e)) for u, e in
+                                     (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
+    if a.sb3_defaults:
+        return PPOConfig.sb3_defaults(**common)
+    return PPOConfig(n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.epochs,
+                     net_arch=tuple(a.net), **common)
 
 
 def main(argv=None):
@@ -113,20 +144,7 @@ def main(argv=None):
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    common = dict(num_envs=a.envs, learning_rate=a.lr, ent_coef=a.ent_coef, seed=a.seed,
-                  grad_buckets=a.grad_buckets,
-                  state_dtype=a.state_dtype, variant=a.variant, initial_eps=a.initial_eps,
-                  bootstrap_timeouts=a.bootstrap_timeouts, **option_values(a),
-                  normalize_obs=a.normalize_obs, normalize_reward=a.normalize_reward,
-                  clip_obs=a.clip_obs, clip_reward=a.clip_reward,
-                  eps_schedule=tuple((int(u), float(e)) for u, e in
-                                     (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
-    if a.sb3_defaults:
-        cfg = PPOConfig.sb3_defaults(**common)
-    else:
-        cfg = PPOConfig(n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.epochs,
-                        net_arch=tuple(a.net), **common)
-    tr = PPOTrainer(cfg, rank=rank, world_size=world)
+    tr = PPOTrainer(config_from_args(a), rank=rank, world_size=world)
     if a.traj_dir and rank == 0:
         from .trajectory import TrajectoryRecorder
         tr.trajectory = TrajectoryRecorder(tr.env, out_dir=a.traj_dir)

@@ -754,6 +754,53 @@ int dr_clip_adam_sched(int64_t n, float *params, float *grads, float *exp_avg,
                        float *grad_norm_out, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* KL control of the optimizer step: SB3's target_kl
+   early stop and a KL-adaptive learning rate, decided on the device by the
+   launch that applies Adam, so a training loop captured into a hipGraph needs
+   no host round trip.  `control` is device memory of num_steps + 1 slots of
+   16 bytes, (stopped u32, taken u32, lr f32, pad); optimizer step `step` of
+   the iteration reads slot `step` and writes slot `step + 1` (the caller
+   fills slot 0: stopped 0, taken 0, the learning rate).  `kl` points at this
+   step's approx_kl (stats[5] of the loss), final before the launch.  In this
+   order:
+     1. slot.stopped: nothing is applied; params, exp_avg, exp_avg_sq and grads
+        stay as they are (grads unclipped), grad_norm_out is still written, the
+        next slot is a copy;
+     2. stop_kl > 0 and kl > stop_kl (false for NaN): stopped <- 1, taken and
+        lr carried, nothing applied (the tripping minibatch is not applied);
+     3. adaptive: kl > kl_high: lr <- max(lr / 1.5f, lr_min); else 0 < kl <
+        kl_low: lr <- min(lr * 1.5f, lr_max) (f32, one rounding per operation);
+     4. clip_grad_norm_ + Adam exactly as dr_clip_adam_sched at grad_scale 1,
+        with the step scalars sched[taken] (`sched`: (num_steps, 2) rows of
+        dr_adam_schedule, 8-byte aligned) -- step_size = sched[taken][0], or
+        with adaptive (a table built at lr 1) lr * sched[taken][0]; the next
+        slot gets (0, taken + 1, lr).
+   Every block of the launch takes the same decision from the same words; there
+   is no atomic, so reruns and graph replays are bitwise equal. */
+typedef struct dr_kl_gate {
+    void *control;
+    int64_t num_steps, step;
+    const float *kl;
+    const float *sched;
+    float stop_kl;                   /* f32(1.5 * target_kl); 0: no target */
+    int32_t adaptive;                /* 0 / 1 */
+    float kl_high, kl_low;           /* 2 * desired_kl, desired_kl / 2 */
+    float lr_min, lr_max;
+} dr_kl_gate;
+
+/* dr_clip_adam_sched (grad_scale 1) and dr_grad_finish_clip_adam_sched behind
+   the gate.  Workspaces as theirs.  (ABI v16.) */
+int dr_clip_adam_kl(int64_t n, float *params, float *grads, float *exp_avg,
+                    float *exp_avg_sq, double beta1, double beta2, double eps,
+                    float max_grad_norm, const dr_kl_gate *gate, float *grad_norm_out,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int dr_grad_finish_clip_adam_kl(const dr_grad_finish *f, int64_t n, float *params,
+                                float *grads, float *exp_avg, float *exp_avg_sq,
+                                double beta1, double beta2, double eps,
+                                float max_grad_norm, const dr_kl_gate *gate,
+                                float *grad_norm_out, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 /* ---- fp32-accurate 256 x 256 layer GEMM on the bf16 matrix cores ---------
    Replaces the torch fp32 Linear of SB3's MlpExtractor 256 -> 256 layer
    (forward z = h W^T and the input gradient grad_h = grad_z W; reference
