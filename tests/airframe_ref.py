@@ -28,10 +28,15 @@ def airframe(seed, gids, ep, spreads):
     return out
 
 
-def airframe_step(state, action):
+def airframe_step(state, action, fault=None):
     """One step for n envs.  `state`: gym_step_batched's dict plus "airframe"
     (n,6) f32, mutated in place (the airframe is read only).  Returns obs
-    (n,15) f32, reward (n,) f64, done (n,) bool."""
+    (n,15) f32, reward (n,) f64, done (n,) bool.
+
+    `fault` selects a deliberately WRONG law, for the tests that show the
+    checks can fail: "gravity" scales the gravity term by 1/m too, "yaw"
+    leaves the yaw torque unscaled by 1/s, "f64_recip" forms 1/m in f64 where
+    the law has the f32 divide."""
     s = state
     af = np.ascontiguousarray(s["airframe"], np.float32)
     a = np.asarray(action, dtype=np.float32)
@@ -40,12 +45,14 @@ def airframe_step(state, action):
     # 2. the reciprocals (f32 divides), then the cast to the state scalar
     im = (np.float32(1.0) / af[:, 0]).astype(np.float64)
     is_ = (np.float32(1.0) / af[:, 1]).astype(np.float64)
+    if fault == "f64_recip":
+        im = 1.0 / af[:, 0].astype(np.float64)
     thrust = ((a0 + a1) + a2) + a3                      # f32
     # 4. the torques scale by 1/s
     tau_phi = (_FACTOR * (((a0 + a1) - a2) - a3)) * is_         # f64
     tau_th = (_FACTOR * (((-a0 + a1) + a2) - a3)) * is_
     tau_psi = np.float32(K_YAW) * (((a0 - a1) + a2) - a3)       # f32
-    tau_psi = tau_psi.astype(np.float64) * is_
+    tau_psi = tau_psi.astype(np.float64) * (1.0 if fault == "yaw" else is_)
     e = s["euler"]
     cph, sph = np.cos(e[:, 0]), np.sin(e[:, 0])
     cth, sth = np.cos(e[:, 1]), np.sin(e[:, 1])
@@ -54,7 +61,7 @@ def airframe_step(state, action):
     # 3. the accelerations use the reciprocal mass scale
     acc = np.stack([0.0 + ((cps * sth * cph + sps * sph) * T) * im,
                     0.0 + ((sps * sth * cph - cps * sph) * T) * im,
-                    -G + ((cth * cph) * T) * im], axis=1)
+                    -G * (im if fault == "gravity" else 1.0) + ((cth * cph) * T) * im], axis=1)
     s["vel"] += acc * DT
     s["pos"] += s["vel"] * DT
     w = s["omega"].copy()

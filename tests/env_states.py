@@ -28,6 +28,17 @@ of 64), and lane i % 32 of wave i // 32 in the 32-rows-per-wave step forms,
 which therefore see each C_lanes pattern as two half waves.  C_lanes is a
 whole number of 64-row waves starting at row 0.
 
+The gym variant's three options are corpus kinds of their own ("wind",
+"waypoint", "airframe": OPTIONS): the same blocks, plus the words that are
+loaded through set().  wind: mean wind and gust per row, block D's finite rows
+also at signed zeros, the largest finite f32 and inf / NaN; the drag moves the
+velocity ahead of the gym step, so block E's positions and targets are derived
+from the restatement's vel_new dt (_wind_block_e).  airframe: m, s and the
+gains inside the largest admitted spreads, at their ends, and at 1.0f in all
+six words.  waypoint: the index j up to 2^24 - 1, eps over {0, 0.5, 1}; block
+E's bonus edge is the f32 reach radius, with rows that reach in the step that
+crashes (and, E being crossed with the time limit, in the step that times out).
+
 The "tag" variant pairs row 2j (pursuer) with row 2j + 1 (evader); every
 block has an even length, so no pair straddles two blocks."""
 import zlib
@@ -40,6 +51,14 @@ MOTOR_MAX = 3 * 1.0 * 9.81 / 4.0
 FAST = 524288.0                     # trig.h: the fast range is |x| < 2^19
 SMOOTH = (0.35, 0.02)               # motor_alpha, rate_penalty of the tests
 TAG = (0.3, 0.5)                    # tag_radius, crash_penalty of the tests
+# The gym variant's options as corpus kinds: the constructor keywords of the
+# tests.  0.3 is no f32 value, so (S)radius differs from the f64 literal; the
+# spreads are the largest check_airframe admits (1/m and 1/s up to 10).
+OPTIONS = {"wind": dict(drag=0.5, wind_speed=2.0, gust_sigma=0.5, gust_rate=0.1),
+           "waypoint": dict(reach_radius=0.3, reach_bonus=1.0),
+           "airframe": dict(mass_spread=0.9, inertia_spread=0.9, motor_spread=0.5)}
+SEED = 7                          # of every batch and of the restatements' draws
+J_TOP = (1 << 24) - 1               # the largest index below the Philox tag's bits
 VEC = ("pos", "vel", "euler", "omega", "target")
 I3 = (0.005, 0.005, 0.01)
 FACTOR = 0.5 / np.sqrt(2.0)
@@ -54,7 +73,17 @@ def max_steps_of(variant):
 
 
 def bonus_edge(variant):
+    """The distance below which the bonus is paid: the kernel's (S)0.05 /
+    (S)1 literal, or the waypoint handle's f32 radius."""
+    if variant == "waypoint":
+        return float(np.float32(OPTIONS["waypoint"]["reach_radius"]))
     return 1.0 if variant == "vectorized" else 0.05
+
+
+def bonus_of(variant):
+    if variant == "waypoint":
+        return float(np.float32(OPTIONS["waypoint"]["reach_bonus"]))
+    return 1.0
 
 
 def rn(x, dtype):
@@ -274,7 +303,12 @@ def _block_e(dtype, variant):
     tag = variant == "tag"
     edge = float(np.float32(TAG[0])) if tag else float(rn(bonus_edge(variant), dtype))
     near = [float(ulp_steps(edge, k, dtype)) for k in range(-3, 4)]
-    offs = [np.eye(3)[k] * r for k in range(3) for r in near]
+    if variant == "waypoint" and dtype == "f64":
+        # between the f64 literal and the handle's f32 radius: reaches, which a
+        # comparison with the literal would miss
+        lit = OPTIONS["waypoint"]["reach_radius"]
+        near += [lit, float(ulp_steps(lit, 1, dtype)), 0.5 * (lit + edge)]
+    offs =[np.eye(3)[k] * r for k in range(3) for r in near]
     gu = _unit(rng, 200)
     offs += list(gu * (edge * (1.0 + ((np.arange(200) % 9) - 4) * float(fi.eps)))[:, None])
     offs = np.array(offs)
@@ -311,6 +345,14 @@ def _block_e(dtype, variant):
             b["pos"] = base
             b["target"] = base + offs
         parts.append(b)
+        if variant == "waypoint":
+            # a reach in the step that also crashes: below the ground or past
+            # the shell, the waypoint a third of the radius away
+            c = _generic(48, rng, variant)
+            c["pos"][:24] = [0.25, -0.125, -tiny]
+            c["pos"][24:] = u[:24] * (50.0 * (1.0 + 8 * float(fi.eps)))
+            c["target"] = c["pos"] + _unit(rng, 48) * (edge / 3)
+            parts.append(c)
     e = _cat(parts)
     n = len(e["step"])
     # the state that holds position: zero command (and motors), vel = (0, 0, RN(g dt))
@@ -351,6 +393,87 @@ def _cat(parts):
     return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
 
+def _wind_words(c, dtype):
+    """(n,6) f32: mean wind uniform in +-2, gust normal(0, 0.5); on finite
+    in-range rows of block D the signed zeros, the largest finite f32 and
+    inf / NaN in each axis of the mean wind and of the gust."""
+    n = c["n"]
+    rng = _rng("wind_words", dtype, "wind")
+    w = np.concatenate([rng.uniform(-2, 2, (n, 3)), rng.normal(0, 0.5, (n, 3))],
+                       1).astype(np.float32)
+    top = np.finfo(np.float32).max
+    pats = [(0.0, 0.0), (-0.0, -0.0), (0.0, -0.0), (top, 0.0), (-top, 0.0), (0.0, top),
+            (0.0, -top), (top, top), (np.inf, 0.0), (-np.inf, 0.0), (0.0, np.inf),
+            (0.0, -np.inf), (np.inf, -np.inf), (np.nan, 0.0), (0.0, np.nan)]
+    d = c["blocks"]["D"]
+    ok = np.ones(n, bool)
+    for k in ("pos", "vel", "euler", "omega"):
+        ok &= np.isfinite(c[k]).all(1)
+    ok &= (np.abs(c["euler"]) < FAST).all(1)
+    cand = np.flatnonzero(ok[d]) + d.start
+    rows = cand[::len(cand) // (3 * len(pats))][:3 * len(pats)]
+    special = np.zeros(n, bool)
+    for r, row in enumerate(rows):
+        m, g = pats[r // 3]
+        if r // 3 < 3:                              # the signed zeros: all six words
+            w[row, :3], w[row, 3:] = m, g
+        else:
+            w[row, r % 3], w[row, 3 + r % 3] = m, g
+        special[row] = True
+    return w, special
+
+
+def _airframe_words(c, dtype):
+    """(n,6) f32: m, s uniform in 1 +- 0.9, the gains in 1 +- 0.5 (1.0f +
+    spread * xi in f32, as the draw forms them); of every 16 rows one at 1.0f in
+    all six words and six with m, s or a gain at exactly 1 -+ spread."""
+    n = c["n"]
+    o = OPTIONS["airframe"]
+    rng = _rng("airframe_words", dtype, "airframe")
+    sp = np.array([o["mass_spread"], o["inertia_spread"]] + [o["motor_spread"]] * 4, np.float32)
+    one = np.float32(1.0)
+    af = one + sp * rng.uniform(-1, 1, (n, 6)).astype(np.float32)
+    r = np.arange(n) % 16
+    af[r == 0] = one
+    for k, (col, sign) in enumerate([(0, -1), (0, 1), (1, -1), (1, 1), (2, -1), (5, 1)], 1):
+        af[r == k, col] = one + np.float32(sign) * sp[col]
+    return af
+
+
+def _waypoint_words(c, dtype):
+    """(n,2) i32 (j, q) with j over {0, 1, 3, 2^24 - 2, 2^24 - 1}, and the
+    curriculum eps (n,) over {0, 0.5, 1}: every pair occurs in every block of
+    15 rows.  The top indices show that the counter word is not truncated
+    where it is OR-ed under the Philox tag."""
+    n = c["n"]
+    rng = _rng("waypoint_words", dtype, "waypoint")
+    j = np.array([0, 1, 3, J_TOP - 1, J_TOP], np.int32)[np.arange(n) % 5]
+    wp = np.stack([j, rng.integers(0, 1000, n).astype(np.int32)], 1)
+    return wp, np.array([0.0, 0.5, 1.0])[np.arange(n) % 3]
+
+
+def _wind_block_e(c, dtype):
+    """The drag moves the velocity ahead of the gym step, so block E does not
+    hold position.  vel_new dt does not depend on pos: taken once from the
+    restatement, each row's pos becomes P - vel_new dt and its target moves
+    with the position the restatement then reaches, P the position (and
+    target - P the offset) the block was designed at.  The rows at pz = 0,
+    +-subnormal, +-tiny become the 0, +-1, +-3 ulp neighbours of -vel_new_z dt."""
+    e = c["blocks"]["E"]
+    s, _, _, _ = oracle_step("wind", c)
+    vdt = s["vel"][e] * DT
+    P, off = c["pos"][e].copy(), c["target"][e] - c["pos"][e]
+    pos = rn(P - vdt, dtype)
+    third = (e.stop - e.start) // 3
+    for t in range(3):
+        for r, k in enumerate((0, 0, 1, -1, 3, -3)):
+            i = t * third + r
+            pos[i, 2] = ulp_steps(rn(-vdt[i, 2], dtype), k, dtype)
+    c["pos"][e] = pos
+    s, _, _, _ = oracle_step("wind", c)
+    c["target"][e] = rn(s["pos"][e] + off, dtype)
+
+
 _BLOCKS = (("C_lanes", _block_c_lanes), ("A", _block_a), ("B", _block_b), ("C", _block_c),
            ("D", _block_d), ("E", _block_e), ("F", _block_f))
 _CACHE = {}
@@ -360,7 +483,11 @@ def corpus(dtype, variant):
     """dict: "blocks" {name: slice}, pos / vel / euler / omega / target (n,3)
     f64 holding state-dtype values, step (n,) i32, action (n,4) f32, "motion"
     (n,9) f32 (moving), "motor" (n,4) f32 (smooth), "pairs" (n,) the
-    partner's row (tag), "n", "max_steps".  A fresh copy on every call."""
+    partner's row (tag), "n", "max_steps".  `variant` may be one of the gym
+    options' kinds (OPTIONS): then the words loaded through set() come too,
+    "wind" (n,6) f32 with "wind_special" (n,) marking block D's extreme rows,
+    "airframe" (n,6) f32, "waypoint" (n,2) i32 with "eps" (n,), and "ep_num"
+    (n,) as a fresh handle reports it.  A fresh copy on every call."""
     key = (dtype, variant)
     if key not in _CACHE:
         parts, blocks, r = [], {}, 0
@@ -388,6 +515,15 @@ def corpus(dtype, variant):
             del c["motor"]
         if variant == "tag":
             c["pairs"] = np.arange(c["n"]) ^ 1
+        if variant in OPTIONS:
+            c["ep_num"] = np.ones(c["n"], np.int32)      # a fresh handle's
+        if variant == "wind":
+            c["wind"], c["wind_special"] = _wind_words(c, dtype)
+            _wind_block_e(c, dtype)
+        if variant == "airframe":
+            c["airframe"] = _airframe_words(c, dtype)
+        if variant == "waypoint":
+            c["waypoint"], c["eps"] = _waypoint_words(c, dtype)
         _CACHE[key] = c
     c = _CACHE[key]
     return {k: (v.copy() if isinstance(v, np.ndarray) else
@@ -407,10 +543,14 @@ AD = ("C_lanes", "A", "B", "C", "D", "pad")
 # ---------------------------------------------------------------------------
 # the oracle over a corpus
 # ---------------------------------------------------------------------------
-def oracle_step(variant, c):
+def oracle_step(variant, c, fault=None):
     """One step of the CPU oracle from corpus `c` (not modified).  Returns
     (state dict after the step, obs, rew, done).  gym / moving / vectorized:
-    oracle.cref; smooth / tag: the NumPy restatements around cref.gym_step."""
+    oracle.cref; smooth / tag / wind / waypoint / airframe: the NumPy
+    restatements (the options' with seed SEED, gids = arange(n) and the
+    corpus' ep_num; waypoint adds "reached" and "d" to the state dict).
+    `fault` names one of a restatement's deliberately wrong forms, for
+    tests/test_env_states_cpu.py."""
     from oracle import cref
     s = {k: np.ascontiguousarray(c[k].copy()) for k in VEC}
     s["step"] = c["step"].astype(np.int32).copy()
@@ -429,6 +569,20 @@ def oracle_step(variant, c):
             from tag_ref import tag_step
             obs, rew, done, crash = tag_step(s, a, TAG[0], TAG[1])
             s["crash"] = crash
+        elif variant == "wind":
+            from wind_ref import wind_step
+            s["wind"], s["ep_num"] = c["wind"].copy(), c["ep_num"]
+            obs, rew, done = wind_step(s, a, OPTIONS["wind"], SEED, np.arange(c["n"]),
+                                       fault=fault)
+        elif variant == "waypoint":
+            from waypoint_ref import waypoint_step
+            s["waypoint"], s["ep_num"], s["eps"] = c["waypoint"].copy(), c["ep_num"], c["eps"]
+            obs, rew, done, s["reached"], s["d"] = waypoint_step(
+                s, a, OPTIONS["waypoint"], SEED, np.arange(c["n"]), fault=fault)
+        elif variant == "airframe":
+            from airframe_ref import airframe_step
+            s["airframe"] = c["airframe"].copy()
+            obs, rew, done = airframe_step(s, a, fault=fault)
         else:
             # the oracle's step counter is shared: one call per distinct step
             n = c["n"]
@@ -453,11 +607,13 @@ def unit_roundoff(dtype):
     return 2.0 ** -53 if dtype == "f64" else 2.0 ** -24
 
 
-def rounding_counts(dtype, out_of_range, kernel=True):
+def rounding_counts(dtype, out_of_range, kernel=True, variant=None):
     """Roundings (in units of u = half an ulp, relative to the envelope)
     behind each state output of one side of a comparison.  See
     tests/test_env_states_gpu.py for the derivation.  `out_of_range` (n,)
-    bool: rows with an angle on the library trig path."""
+    bool: rows with an angle on the library trig path.  `variant` matters
+    for the gym options' kinds only: "wind" adds the drag impulse's roundings
+    to vel, "airframe" the reciprocal products' to vel and omega."""
     K = 1.0 if (dtype == "f32" and kernel) else 0.0     # constants rounded to f32
     if kernel:
         # fast path: 1 ulp (f64) / 2 ulp (f32) from the correctly rounded
@@ -470,21 +626,29 @@ def rounding_counts(dtype, out_of_range, kernel=True):
         S = np.full(out_of_range.shape, 2.0)            # glibc / numpy: 1 ulp
         tan = np.full(out_of_range.shape, 2.0)
     vel = 3 * S + 6 + 2 * K
+    omg = np.full(out_of_range.shape, 8 + 4 * K)
+    if variant == "wind":
+        # v' = v + ((k (w - v)) dt): the difference, x k, x dt (+K), the sum;
+        # w and (S)k are exact casts
+        vel = vel + 4 + K
+    if variant == "airframe":
+        # x (S)im where the gym's / kMass is exact; x (S)is on each torque
+        vel = vel + 1
+        omg = omg + 1
     pos = vel + 2 + K
     eul = S + tan + 6 + K
-    omg = np.full(out_of_range.shape, 8 + 4 * K)
     rew = pos + 7 + K
     return {"vel": vel, "pos": pos, "euler": eul, "omega": omg, "rew": rew}
 
 
-def bound_counts(dtype, out_of_range, both_cpu=False):
+def bound_counts(dtype, out_of_range, both_cpu=False, variant=None):
     """c per row and output: kernel side + reference side.  The f64 oracle
     has the kernel's operations with 1 ulp library trig; against an f32
     kernel its whole error is below one f32 rounding."""
-    ref = rounding_counts("f64", out_of_range, kernel=False)
+    ref = rounding_counts("f64", out_of_range, kernel=False, variant=variant)
     if both_cpu:
         return {k: 2 * ref[k] for k in ref}
-    ker = rounding_counts(dtype, out_of_range, kernel=True)
+    ker = rounding_counts(dtype, out_of_range, kernel=True, variant=variant)
     if dtype == "f64":
         return {k: ker[k] + ref[k] for k in ker}
     return {k: ker[k] + 1 for k in ker}
@@ -494,7 +658,10 @@ def envelopes(variant, c, tgt_new=None):
     """The value expressions of one step with every term replaced by its
     absolute value, from the pre-step corpus `c` (f64 numpy): dict of (n,3)
     arrays for vel / pos / euler / omega and (n,) "rew" (without the bonus and
-    the f32-side terms, which the caller adds)."""
+    the f32-side terms, which the caller adds).  wind: |v| + k (|w| + |v|) dt
+    stands where |v| does, w the f32 sum of the mean wind and the updated gust;
+    airframe: the gained command, 1/m on the thrust terms, 1/s on the
+    torques."""
     with np.errstate(all="ignore"):
         e = c["euler"]
         sph, cph = np.abs(np.sin(e[:, 0])), np.abs(np.cos(e[:, 0]))
@@ -504,14 +671,24 @@ def envelopes(variant, c, tgt_new=None):
         if variant == "smooth":
             al = np.float32(SMOOTH[0])
             a = (np.float32(1.0) - al) * c["motor"] + al * a
+        im = isc = 1.0
+        if variant == "airframe":
+            af = c["airframe"]
+            a = af[:, 2:] * a
+            im = (np.float32(1.0) / af[:, 0]).astype(np.float64)
+            isc = (np.float32(1.0) / af[:, 1]).astype(np.float64)
+        v0 = np.abs(c["vel"])
+        if variant == "wind":
+            w = np.abs((c["wind"][:, :3] + gust_after(c)).astype(np.float64))
+            v0 = v0 + (float(np.float32(OPTIONS["wind"]["drag"])) * (w + v0)) * DT
         a0, a1, a2, a3 = (a[:, k] for k in range(4))
         T = np.abs((((a0 + a1) + a2) + a3).astype(np.float64))
         mphi = np.abs((((a0 + a1) - a2) - a3).astype(np.float64))
         mth = np.abs((((-a0 + a1) + a2) - a3).astype(np.float64))
         mpsi = np.abs((np.float32(0.01) * (((a0 - a1) + a2) - a3)).astype(np.float64))
-        acc = np.stack([(cps * sth * cph + sps * sph) * T, (sps * sth * cph + cps * sph) * T,
-                        G + (cth * cph) * T], 1)
-        vel = np.abs(c["vel"]) + acc * DT
+        acc = np.stack([(cps * sth * cph + sps * sph) * T * im,
+                        (sps * sth * cph + cps * sph) * T * im, G + (cth * cph) * T * im], 1)
+        vel = v0 + acc * DT
         pos = np.abs(c["pos"]) + vel * DT
         w = np.abs(c["omega"])
         tth = sth / cth
@@ -519,9 +696,9 @@ def envelopes(variant, c, tgt_new=None):
                        cph * w[:, 1] + sph * w[:, 2],
                        (sph / cth) * w[:, 1] + (cph / cth) * w[:, 2]], 1)
         eul = np.abs(e) + ed * DT
-        wd = np.stack([(FACTOR * mphi + abs(I3[1] - I3[2]) * w[:, 1] * w[:, 2]) / I3[0],
-                       (FACTOR * mth + abs(I3[2] - I3[0]) * w[:, 0] * w[:, 2]) / I3[1],
-                       (mpsi + abs(I3[0] - I3[1]) * w[:, 0] * w[:, 1]) / I3[2]], 1)
+        wd = np.stack([(FACTOR * mphi * isc + abs(I3[1] - I3[2]) * w[:, 1] * w[:, 2]) / I3[0],
+                       (FACTOR * mth * isc + abs(I3[2] - I3[0]) * w[:, 0] * w[:, 2]) / I3[1],
+                       (mpsi * isc + abs(I3[0] - I3[1]) * w[:, 0] * w[:, 1]) / I3[2]], 1)
         omg = w + wd * DT
         if variant == "tag":
             other = pos[c["pairs"]]
@@ -604,13 +781,73 @@ def reward_exact(variant, dtype, pos_new, target, crash=None, dev_sq=None):
             r = np.where(np.arange(len(p)) % 2 == 0, g, -g)
         else:
             r = f(0.01) * -d
-            r = np.where(d < f(0.05), r + f(1), r)
+            r = np.where(d < f(bonus_edge(variant)), r + f(bonus_of(variant)), r)
         rf = r.astype(np.float32)
         if variant == "smooth" and SMOOTH[1] != 0:
             rf = rf - np.float32(SMOOTH[1]) * dev_sq
         if variant == "tag" and TAG[1] != 0:
             rf = np.where(crash, rf - np.float32(TAG[1]), rf).astype(np.float32)
     return rf.astype(np.float32)
+
+
+def gust_after(c):
+    """(n,3) f32: the wind corpus' gust after one step, wind_ref.gust_update
+    on the step's own noise (three f32 roundings per element)."""
+    import wind_ref
+    o = OPTIONS["wind"]
+    xi = wind_ref.gust_noise(SEED, np.arange(c["n"]), c["ep_num"], c["step"])
+    with np.errstate(all="ignore"):
+        return wind_ref.gust_update(c["wind"][:, 3:], xi,
+                                    *wind_ref.gust_coefficients(o["gust_sigma"], o["gust_rate"]))
+
+
+def reached_exact(dtype, pos_new, target):
+    """The waypoint option's reach flag from the position the kernel stored
+    and the waypoint the step started with: d < (S)R in numpy of the state
+    dtype, d the reward's distance (NaN compares false)."""
+    f = ftype(dtype)
+    with np.errstate(all="ignore"):
+        d3 = np.asarray(pos_new, np.float64).astype(f) - np.asarray(target, np.float64).astype(f)
+        d = np.sqrt((d3[:, 0] * d3[:, 0] + d3[:, 1] * d3[:, 1]) + d3[:, 2] * d3[:, 2])
+        return d < f(bonus_edge("waypoint"))
+
+
+def option_exact_failures(variant, dtype, c, got):
+    """What a step must leave in an option's words, exactly, given the
+    position it stored: `got` holds "pos" and "target" after the step and the
+    option's field.  Returns the names of the checks that fail.
+
+      wind      the mean wind unchanged, the gust bitwise wind_ref.gust_update
+                (f32 in both state dtypes), non-finite rows included
+      airframe  the six words untouched
+      waypoint  reached = d < (S)R from the stored position and the OLD
+                waypoint; (j, q) advanced by one on those rows and untouched
+                elsewhere; the new target bitwise waypoint_ref.waypoint cast to
+                the state dtype, (0, 0, 1) where eps == 0, the old one on the
+                other rows"""
+    n, bad = c["n"], []
+    if variant == "wind":
+        if not same_bits_or_nan(got["wind"][:, :3], c["wind"][:, :3]).all():
+            bad.append("mean wind")
+        if not same_bits_or_nan(got["wind"][:, 3:], gust_after(c)).all():
+            bad.append("gust")
+    if variant == "airframe":
+        if not same_bits_or_nan(got["airframe"], c["airframe"]).all():
+            bad.append("airframe words")
+    if variant == "waypoint":
+        import waypoint_ref
+        reached = reached_exact(dtype, got["pos"], c["target"])
+        wp = c["waypoint"] + reached[:, None].astype(np.int32)
+        if not np.array_equal(got["waypoint"], wp):
+            bad.append("counters")
+        tgt = c["target"].copy()
+        tgt[reached] = rn(waypoint_ref.waypoint(SEED, np.arange(n)[reached], c["ep_num"][reached],
+                                                wp[reached, 0], c["eps"][reached]), dtype)
+        z = reached & (c["eps"] == 0)
+        assert z.sum() >= 20 and (tgt[z] == [0.0, 0.0, 1.0]).all()
+        if not same_bits_or_nan(np.asarray(got["target"], np.float64), tgt).all():
+            bad.append("target")
+    return bad
 
 
 def smooth_dev_sq(c):

@@ -16,17 +16,22 @@ import env_states as es
 TD = {"f64": torch.float64, "f32": torch.float32}
 K = 4
 FIELDS = ("pos", "vel", "euler", "omega", "target", "current_step")
+OPTION_FIELDS = ("wind", "waypoint", "airframe")
 
 
 def new_batch(variant, dtype, c, auto_reset, **kw):
     """A batch of the corpus' size holding the corpus' state.  smooth runs at
-    a non-neutral lag and penalty, tag at a non-zero crash penalty."""
+    a non-neutral lag and penalty, tag at a non-zero crash penalty; the kinds
+    of es.OPTIONS are the gym variant with the option's keywords."""
     from drone_rl_amd import DroneBatch
     if variant == "smooth":
         kw.update(motor_alpha=es.SMOOTH[0], rate_penalty=es.SMOOTH[1])
     if variant == "tag":
         kw.update(tag_radius=es.TAG[0], crash_penalty=es.TAG[1])
-    b = DroneBatch(c["n"], variant, dtype=TD[dtype], auto_reset=auto_reset, seed=7, **kw)
+    if variant in es.OPTIONS:
+        kw.update(es.OPTIONS[variant])
+        variant = "gym"
+    b = DroneBatch(c["n"], variant, dtype=TD[dtype], auto_reset=auto_reset, seed=es.SEED, **kw)
     load(b, c)
     return b
 
@@ -41,6 +46,13 @@ def load(b, c):
         b.set("motion", c["motion"])
     if b.variant == "smooth":
         b.set("motor", c["motor"])
+    for k in OPTION_FIELDS:
+        if k in c:
+            b.set(k, c[k])
+    if "waypoint" in c:
+        b.set("eps", c["eps"])
+    if "ep_num" in c:
+        assert np.array_equal(b.get("ep_num").cpu().numpy(), c["ep_num"])
 
 
 def fields(b):
@@ -52,6 +64,9 @@ def fields(b):
         out["motion"] = b.get("motion")
     if b.variant == "smooth":
         out["motor"] = b.get("motor")
+    for k, on in zip(OPTION_FIELDS, (b.wind_enabled, b.waypoints_enabled, b.airframe_enabled)):
+        if on:
+            out[k] = b.get(k)
     return out
 
 

@@ -2,8 +2,9 @@
 out-of-range trig branch, the fast range's boundary, gimbal lock, the
 termination and bonus thresholds at their edges, and non-finite state.
 
-a. test_step_matches_oracle: one dr_step of every variant and dtype against
-   the CPU oracle.
+a. test_step_matches_oracle: one dr_step of every variant and dtype, and of
+   the gym variant under each of its options (wind, waypoint courses,
+   airframe randomisation), against the CPU oracle.
 b. test_device_sincos_ulps: the device's sin / cos against mpmath, read
    through state words one or two roundings away.
 c. test_step_forms_bitwise / test_rollout_*: every kernel form against the
@@ -37,6 +38,27 @@ result, is at most u x envelope.  c counts those roundings
        the root (1), x 0.01 (1 + K), + bonus (1):       pos + 7 + K
        then the f32 casts, 2^-24 |r| each, added outside gamma.
 
+The gym options (kinds "wind", "waypoint", "airframe" of env_states.OPTIONS)
+change these lines, on both sides of the comparison alike (the restatements
+tests/wind_ref.py, waypoint_ref.py, airframe_ref.py are f64 and have the
+kernel's operations):
+
+  wind      the pre-step v' = v + ((k (w - v)) dt) stands where v does.  w =
+            (S)(m + g') is the exact cast of an f32 sum and (S)k an exact
+            cast; the difference (1), x k (1), x dt (1 + K), the sum (1):
+                                                        vel + 4 + K
+            pos and rew follow from vel.  Envelope: |v| + k (|w| + |v|) dt
+            in place of |v|.  The gust g' = b g + c xi is f32 in both state
+            dtypes and compared bitwise with wind_ref.gust_update.
+  airframe  x (S)im replaces the exact / kMass:         vel + 1
+            x (S)is on each of the three torques:       omg + 1
+            im = 1.0f / m and is = 1.0f / s are f32 divides on both sides
+            (equal inputs, no rounding counted); the gained command g_j a_j
+            is f32 on both sides too.  Envelope: 1/m on the thrust terms (not
+            on g), 1/s on the torques, up to 10 at the spreads' ends.
+  waypoint  the physics and its counts are the gym's; reached = d < (S)R, the
+            counters and the new target are exact (option_exact_failures).
+
 c = kernel side + oracle side in f64 (15 + 12 = 27 for vel on the fast path,
 30 + 12 = 42 on the library path); in f32 the f64 oracle's whole error is
 below one f32 rounding: kernel side + 1.  None of this is taken from what the
@@ -59,6 +81,27 @@ kernel produces.  Measured worst |got - ref| / (u x envelope) on the MI355X
 
 (omega 0.00 in f64: div_rcp gave the IEEE quotient's bits on every row.)
 
+The gym options, measured the same way (c: wind f64 pos 39..54, vel 35..50,
+f32 pos 32..41, vel 29..38; airframe f64 pos 33..48, vel 29..44, omega 18, f32
+pos 28..37, vel 25..34, omega 14; waypoint and every other count as gym's);
+reach flips = f32 `reached` differing from the f64 restatement's, all in block
+E:
+
+  kind        dtype  pos   vel   euler  omega  rew    flips  reach flips
+  wind        f64    2.11  3.57  5.08   0.00   0.333  0
+  wind        f32    2.27  3.47  4.05   3.48   0.025  158
+  waypoint    f64    1.81  3.83  5.34   0.00   0.331  0      0
+  waypoint    f32    1.99  3.34  4.31   3.20   0.023  134    36
+  airframe    f64    2.40  4.15  3.78   0.00   0.330  0
+  airframe    f32    2.82  3.89  3.52   3.83   0.026  118
+
+(waypoint: 506 reaches in f64, 465 of them in block E and 251 in a step that
+also ends the episode; 369 rows of E miss by less than 1e-6.  wind f32: the
+rows at the largest finite f32 wind reach |pos| = 6.8e34, where the f32
+squares of the reward's distance overflow: the kernel's reward is -inf there,
+as the f32 recomputation from its stored position has it, and the f64
+restatement's is finite; those rows are compared with the recomputation only.)
+
 `done` is exact: equal to the oracle on every row in f64, on blocks A-D in
 f32 (tests/test_env_states_cpu.py shows those rows >= 1e-3 from every
 threshold), and in both dtypes equal to the reference's own predicate
@@ -77,6 +120,7 @@ from subproc import run_worker
 
 pytestmark = pytest.mark.gpu
 VARIANTS = ("gym", "moving", "smooth", "tag", "vectorized")
+KINDS = tuple(es.OPTIONS)               # the gym options: wind, waypoint, airframe
 DTYPES = ("f64", "f32")
 U32 = 2.0 ** -24
 
@@ -95,7 +139,7 @@ def _moved_target(c, step_new):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("variant", VARIANTS + KINDS)
 def test_step_matches_oracle(variant, dtype):
     c = es.corpus(dtype, variant)
     n, f, u = c["n"], es.ftype(dtype), es.unit_roundoff(dtype)
@@ -104,6 +148,7 @@ def test_step_matches_oracle(variant, dtype):
     obs, rew, done = _np(obs), _np(rew), _np(done).astype(bool)
     got = {k: _np(b.get(k)) for k in ("pos", "vel", "euler", "omega")}
     step = _np(b.get("current_step"))
+    tgt_new = _np(b.get("target")) if variant == "waypoint" else None
     ref, ro, rr, rd = es.oracle_step(variant, c)
     ad = es.rows_of(c, es.AD)
 
@@ -145,7 +190,8 @@ def test_step_matches_oracle(variant, dtype):
             assert es.same_bits_or_nan(obs[:, 12:18], ext).all()
             assert np.array_equal(obs[:, 18], np.where(np.arange(n) % 2 == 0, 1, -1))
         elif variant != "vectorized":
-            rel = (tgt.astype(f) - ps).astype(np.float32)
+            # waypoint: the stored target is the new one on the reach rows
+            rel = ((tgt if tgt_new is None else tgt_new).astype(f) - ps).astype(np.float32)
             assert es.same_bits_or_nan(obs[exact_rows, 12:15], rel[exact_rows]).all()
         if variant == "smooth":
             al = np.float32(es.SMOOTH[0])
@@ -161,7 +207,17 @@ def test_step_matches_oracle(variant, dtype):
     # ---- non-finite entries ---------------------------------------------------
     for k in got:
         assert es.same_nonfinite(got[k], ref[k]), k
-    assert es.same_nonfinite(rew, rr)
+    # f32 squares overflow where |pos - target| passes 1.8e19 (the wind kind's
+    # rows at the largest finite f32): there the kernel's distance is inf and
+    # its reward -inf, as reward_exact has it above, and the f64 oracle's finite
+    sq_over = np.zeros(n, bool)
+    if dtype == "f32" and variant != "tag":
+        with np.errstate(all="ignore"):
+            d2 = ((ref["pos"] - tgt) ** 2).sum(1)
+            sq_over = np.isfinite(d2) & (d2 > float(np.finfo(np.float32).max))
+        assert sq_over.sum() == 0 if variant != "wind" else 6 <= sq_over.sum() <= 15
+        assert (rew[sq_over] == -np.inf).all() and np.isfinite(rr[sq_over]).all()
+    assert es.same_nonfinite(rew[~sq_over], rr[~sq_over])
     with np.errstate(over="ignore"):
         assert np.isinf(st12.astype(np.float32)).sum() == np.isinf(obs[:, :12]).sum()
     if dtype == "f64":
@@ -169,7 +225,7 @@ def test_step_matches_oracle(variant, dtype):
 
     # ---- floats ---------------------------------------------------------------
     oor = (~(np.abs(c["euler"]) < es.FAST)).any(1)
-    cnt = es.bound_counts(dtype, oor)
+    cnt = es.bound_counts(dtype, oor, variant=variant)
     tnew = None
     amp = np.zeros(n)
     if variant == "moving":
@@ -199,7 +255,7 @@ def test_step_matches_oracle(variant, dtype):
             extra = extra + 3 * U32 * np.float64(es.SMOOTH[1]) * dev_sq
         if variant == "tag":
             extra = extra + 3 * U32 * es.TAG[1]
-        fin = np.isfinite(rr) & clear
+        fin = np.isfinite(rr) & clear & ~sq_over
         if variant == "tag":
             # the crash penalty is a step too: f32 may cross a threshold the
             # f64 oracle does not (block E only; never in f64)
@@ -212,6 +268,36 @@ def test_step_matches_oracle(variant, dtype):
         assert clear.mean() > 0.9
         line.append(f"rew {np.max(np.where(fin, err / lim, 0.0)):.3f} of its bound")
     print(f"{variant} {dtype}: worst |got - ref| / (u x envelope): " + ", ".join(line))
+
+    # ---- the options' own words, exact -------------------------------------------
+    if variant in KINDS:
+        gx = {"pos": got["pos"], "target": _np(b.get("target")), variant: _np(b.get(variant))}
+        assert es.option_exact_failures(variant, dtype, c, gx) == []
+    if variant == "waypoint":
+        reached = es.reached_exact(dtype, got["pos"], tgt)
+        near = ~reached & (np.abs(ref["d"] - edge) < 1e-6)
+        ended = reached & done
+        print(f"waypoint {dtype}: reaches {int(reached.sum())} (block E {int(reached[e].sum())}, "
+              f"in a step that ends {int(ended.sum())}), near misses in E {int(near[e].sum())}, "
+              f"reach flips vs oracle {int((reached != ref['reached']).sum())}")
+        assert reached[e].sum() >= 20 and near[e].sum() >= 20 and ended.sum() >= 40
+        assert not (reached != ref["reached"])[ad].any()
+        if dtype == "f64":
+            assert np.array_equal(reached, ref["reached"])
+    if variant == "airframe":
+        # the rows at 1.0f in all six words are the gym kernel's rows
+        ones = (c["airframe"] == 1).all(1)
+        assert ones.sum() >= 500
+        g = new_batch("gym", dtype, {k: v for k, v in c.items() if k != "airframe"}, False)
+        go, gr, gd = g.step(torch.from_numpy(c["action"]).cuda())
+        for name, x, y in [("obs", obs, _np(go)), ("rew", rew, _np(gr)),
+                           ("done", done, _np(gd).astype(bool))] + \
+                [(k, got[k], _np(g.get(k))) for k in got]:
+            same = es.same_bits_or_nan(x, y) if x.dtype.kind == "f" else x == y
+            assert same[ones].all(), name
+            if name in ("vel", "omega"):
+                assert not same[~ones].all(), name      # the option is live elsewhere
+        g.close()
     b.close()
 
 
@@ -449,7 +535,8 @@ def _baseline(variant, dtype, monkeypatch):
 
 
 @pytest.mark.parametrize("variant,dtype", [(v, "f64") for v in VARIANTS] + [("gym", "f32"),
-                                                                           ("tag", "f32")])
+                                                                           ("tag", "f32")] +
+                         [(v, "f64") for v in KINDS] + [("waypoint", "f32")])
 def test_step_forms_bitwise(variant, dtype, monkeypatch):
     """K = 4 dr_step launches with auto_reset from the corpus: 32 rows per
     wave and nontemporal state loads (the forms dr_create picks by batch
@@ -475,8 +562,12 @@ def test_step_forms_bitwise(variant, dtype, monkeypatch):
         so, sr, sd = b.step(acts[t], trunc_out=trunc)
         o.append(so.clone()), r.append(sr.clone()), d.append(sd.clone())
         if t == 0 and variant != "vectorized":
-            # crash and time limit in one step: not a truncation
-            _, crash = es.done_predicate(variant, dtype, c["pos"], c["step"] + 1, c["max_steps"])
+            # crash and time limit in one step: not a truncation (block E holds
+            # position; under wind it moves, to where the restatement has it:
+            # at zero thrust no trig enters and the f64 kernel's position is
+            # the restatement's bit for bit)
+            pos1 = es.oracle_step(variant, c)[0]["pos"] if variant == "wind" else c["pos"]
+            _, crash = es.done_predicate(variant, dtype, pos1, c["step"] + 1, c["max_steps"])
             e = es.rows_of(c, ("E",)) & np.isfinite(c["pos"]).all(1)
             if variant == "tag":
                 crash = crash | crash[c["pairs"]]
@@ -501,11 +592,12 @@ def test_step_forms_bitwise(variant, dtype, monkeypatch):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("variant", VARIANTS + KINDS)
 def test_rollout_default_form_bitwise(variant, dtype):
     """dr_rollout in the form the size rule picks at the corpus' size (the
     split-physics kernel for gym, the warp-specialised one for moving and
-    vectorized, the one-role kernel for smooth and tag) against K dr_step
+    vectorized, the one-role kernel for smooth, tag and the gym options, whose
+    words block F's resets redraw inside the launch) against K dr_step
     launches, resets from non-finite and out-of-range angles inside the
     launch: env_states_worker.check_rollout."""
     check_rollout(variant, dtype, "default form")

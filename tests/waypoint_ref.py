@@ -29,12 +29,16 @@ def distance(pos, target):
     return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
 
 
-def waypoint_step(state, action, params, seed, gids):
+def waypoint_step(state, action, params, seed, gids, fault=None):
     """One step for n envs.  `state`: cref.gym_step's dict plus "waypoint"
     (n,2) i32 (j, q), "ep_num" (n,) and "eps" (n,) f64, mutated in place;
     `params`: dict of reach_radius, reach_bonus.  Returns obs (n,15) f32,
     reward (n,) f64, done (n,) bool, and what the tests look at besides: the
-    reached mask and the distance d."""
+    reached mask and the distance d.
+
+    `fault` selects a deliberately WRONG law, for the tests that show the
+    checks can fail: "reach_le" reaches at d <= R, "reward_new" takes the
+    reward's distance to the waypoint the step ends with."""
     c = np.ascontiguousarray(state["target"], np.float64)
     state["target"] = c
     obs, _, done = cref.gym_step(state, action)
@@ -43,7 +47,7 @@ def waypoint_step(state, action, params, seed, gids):
     d = distance(state["pos"], c)
     rew = 0.01 * (-d)
     with np.errstate(invalid="ignore"):
-        reached = d < R                     # NaN compares false
+        reached = d <= R if fault == "reach_le" else d < R      # NaN compares false
     rew = np.where(reached, rew + B, rew)
     wp = np.array(state["waypoint"], np.int32)
     wp[reached] += 1
@@ -55,4 +59,7 @@ def waypoint_step(state, action, params, seed, gids):
         c[reached] = waypoint(seed, gids[reached], ep[reached], wp[reached, 0], eps[reached])
         obs = obs.copy()
         obs[reached, 12:15] = (c[reached] - state["pos"][reached]).astype(np.float32)
+    if fault == "reward_new":
+        rew = 0.01 * (-distance(state["pos"], c))
+        rew = np.where(reached, rew + B, rew)
     return obs, rew, done, reached, d

@@ -41,18 +41,29 @@ def gust_update(g, xi, b, c):
     return np.float32(b) * g + np.float32(c) * xi
 
 
-def wind_step(state, action, params, seed, gids):
+def wind_step(state, action, params, seed, gids, fault=None):
     """One step for n envs.  `state`: cref.gym_step's dict plus "wind" (n,6)
     f32 (mean wind xyz, gust xyz) and "ep_num" (n,), mutated in place;
     `params`: dict of drag, wind_speed, gust_sigma, gust_rate.  Returns obs
-    (n,15) f32, reward (n,) f64, done (n,) bool: the gym's."""
+    (n,15) f32, reward (n,) f64, done (n,) bool: the gym's.
+
+    `fault` selects a deliberately WRONG law, for the tests that show the
+    checks can fail: "no_gust" leaves the gust out of the air's velocity,
+    "drag_after" takes the drag impulse on the velocity the gym step leaves
+    (and carries it into the position)."""
     w6 = np.ascontiguousarray(state["wind"], np.float32)
     b, c = gust_coefficients(params["gust_sigma"], params["gust_rate"])
     xi = gust_noise(seed, gids, state["ep_num"], state["step"])
     g = gust_update(w6[:, 3:], xi, b, c)
-    w = (w6[:, :3] + g).astype(np.float64)
+    w = (w6[:, :3] if fault == "no_gust" else w6[:, :3] + g).astype(np.float64)
     k = np.float64(np.float32(params["drag"]))
+    state["wind"] = np.concatenate([w6[:, :3], g], 1)
+    if fault == "drag_after":
+        out = cref.gym_step(state, action)
+        dv = (k * (w - state["vel"])) * DT
+        state["vel"] = state["vel"] + dv
+        state["pos"] = state["pos"] + dv * DT
+        return out
     v = state["vel"]
     state["vel"] = np.ascontiguousarray(v + (k * (w - v)) * DT)
-    state["wind"] = np.concatenate([w6[:, :3], g], 1)
     return cref.gym_step(state, action)
