@@ -37,6 +37,8 @@ DR_RNG_HOST_UNIFORMS = 1
 DR_VECNORM_OBS = 1
 DR_VECNORM_REWARD = 2
 DR_VECNORM_TRAINING = 4
+DR_SENSOR_MAX_DIM = 24
+DR_SENSOR_MAX_DELAY = 15
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
@@ -73,6 +75,13 @@ class dr_kl_gate(ctypes.Structure):
                 ("kl", c_void_p), ("sched", c_void_p), ("stop_kl", c_float),
                 ("adaptive", c_int32), ("kl_high", c_float), ("kl_low", c_float),
                 ("lr_min", c_float), ("lr_max", c_float)]
+
+
+class dr_sensor_config(ctypes.Structure):
+    """include/dronerl.h dr_sensor_config (SensorModel)."""
+    _fields_ = [("delay_lo", c_int32), ("delay_hi", c_int32), ("seed", c_uint64),
+                ("env_id_offset", c_int64), ("sigma", c_float * DR_SENSOR_MAX_DIM),
+                ("beta", c_float * DR_SENSOR_MAX_DIM), ("mirror", c_int32 * DR_SENSOR_MAX_DIM)]
 
 
 class DroneRLError(RuntimeError):
@@ -185,6 +194,8 @@ SIGNATURES = {
                                 c_double, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "dr_vecnorm_apply": (c_int, [c_int64, c_int64, _P, _P, c_double, c_double, _P, _P]),
     "dr_vecnorm_unapply": (c_int, [c_int64, c_int64, _P, _P, c_double, _P, _P]),
+    "dr_sensor_reset": (c_int, [POINTER(dr_sensor_config), c_int64, c_int64] + [_P] * 6),
+    "dr_sensor_step": (c_int, [POINTER(dr_sensor_config), c_int64, c_int64] + [_P] * 9),
 }
 
 _lib = None

@@ -2745,3 +2745,6 @@ int dr_first_layer_backward2(int64_t m, int64_t k, int64_t n, const float *x,
 
 // KL control of the optimizer step (dr_*_clip_adam_kl): likewise.
 #include "kl_control.hip"
+
+// SensorModel (dr_sensor_*): likewise.
+#include "sensor.hip"

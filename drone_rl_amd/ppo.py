@@ -146,6 +146,14 @@ class PPOConfig:
     desired_kl: float = 0.01
     lr_min: float = 1e-6
     lr_max: float = 1e-2
+    # the sensor model between the env and everything that reads observations
+    # (DESIGN.md section 23), all neutral by default: the noise stds and the
+    # per-episode bias half-widths of the (pos, vel, att, rate) columns and the
+    # (lo, hi) steps a per-episode latency is drawn from, hi <= 15.  Any
+    # variant, any env option, any world size; the obs width stays
+    obs_noise: tuple = (0, 0, 0, 0)
+    obs_bias: tuple = (0, 0, 0, 0)
+    obs_delay: tuple = (0, 0)
 
     def __post_init__(self):
         if self.variant not in OBS_DIM:
@@ -154,6 +162,10 @@ class PPOConfig:
         K.check_vecnorm(self.clip_obs, self.clip_reward, self.norm_epsilon, self.gamma)
         K.check_kl_control(self.target_kl, self.lr_schedule, self.desired_kl, self.lr_min,
                            self.lr_max)
+        K.check_sensor(self.obs_noise, self.obs_bias, self.obs_delay)
+
+    def sensor_on(self) -> bool:
+        return not K.sensor_neutral(self.obs_noise, self.obs_bias, self.obs_delay)
 
     def kl_control_on(self) -> bool:
         return self.target_kl is not None or self.lr_schedule != "constant"
@@ -297,6 +309,10 @@ class PPOTrainer:
         if cfg.normalize_obs or cfg.normalize_reward:
             self._enable_vecnorm(cfg.normalize_obs, cfg.normalize_reward, cfg.clip_obs,
                                  cfg.clip_reward, cfg.norm_epsilon)
+        # the sensor model (off: nothing allocated, the launches of before)
+        self.sensor = None
+        if cfg.sensor_on():
+            self._enable_sensor(cfg.obs_noise, cfg.obs_bias, cfg.obs_delay)
         # KL control (off: nothing allocated, the launches of before)
         self._kl, self.stop_kl = None, None
         self._kl_host, self._kl_event = None, None
@@ -420,13 +436,38 @@ class PPOTrainer:
                                        norm_epsilon=float(epsilon))
         self._rgraph = None
 
+    # ------------------------------------------------------------ SensorModel
+    def _enable_sensor(self, noise, bias, delay):
+        """Put the sensor model behind the env: the env writes its clean
+        observation into scratch, the sensor writes what the policy sees into
+        obs[t + 1] (into the normaliser's raw scratch when that is on too).
+        Keyed by the trainer's seed and its rank's global env ids: nothing is
+        shared between ranks."""
+        noise, bias, delay = K.check_sensor(noise, bias, delay, max_steps=self.env.max_steps)
+        N, od, dev = self.cfg.num_envs, self.env.obs_dim, self.device
+        self.sensor = K.SensorModel(N, od, dev,
+                                    columns=K.sensor_columns(self.cfg.variant, noise, bias),
+                                    delay=delay, seed=self.cfg.seed,
+                                    env_id_offset=D.env_shard(self.rank, N)[0])
+        self._clean_obs = torch.zeros(N, od, dtype=torch.float32, device=dev)
+        # bootstrap_timeouts: what the policy would have seen of the terminal obs
+        self._term_seen = torch.zeros(N, od, dtype=torch.float32, device=dev) \
+            if self.cfg.bootstrap_timeouts else None
+        self.cfg = dataclasses.replace(self.cfg, obs_noise=noise, obs_bias=bias, obs_delay=delay)
+        self._rgraph = None
+
     def _reset_env(self):
-        """Reset every env into obs[0] (through the normaliser when on)."""
-        if self.vecnorm is None:
-            self.env.reset(self.obs[0])
+        """Reset every env into obs[0] (through the sensor model, then the
+        normaliser, when on)."""
+        sm, vn = self.sensor, self.vecnorm
+        seen = self.obs[0] if vn is None else self._raw_obs
+        if sm is None:
+            self.env.reset(seen)
         else:
-            self.env.reset(self._raw_obs)
-            self.vecnorm.reset(self._raw_obs, out=self.obs[0])
+            self.env.reset(self._clean_obs)
+            sm.reset(self._clean_obs, out=seen)
+        if vn is not None:
+            vn.reset(self._raw_obs, out=self.obs[0])
 
     # ------------------------------------------------------------ DP plumbing
     def sync_params(self):
@@ -504,12 +545,22 @@ class PPOTrainer:
             # VecMonitor outputs land in this step's slice (done rows only)
             self.env.ep_ret = self.ep_ret[t]
             self.env.ep_len = self.ep_len[t]
-            vn = self.vecnorm
-            self.env.step(self.act_env, obs_out=self.obs[t + 1] if vn is None else self._raw_obs,
+            vn, sm = self.vecnorm, self.sensor
+            seen = self.obs[t + 1] if vn is None else self._raw_obs
+            self.env.step(self.act_env, obs_out=seen if sm is None else self._clean_obs,
                           rew_out=self.rewards[t] if vn is None else self._raw_rew,
                           done_out=self.dones[t + 1],
                           trunc_out=None if self.trunc is None else self.trunc[t])
             term = self.env.term_obs
+            if sm is not None:
+                # env -> sensor -> (normaliser): the clean scratch becomes what
+                # the policy sees, the terminal obs of done envs likewise
+                if self.trunc is None:
+                    sm.step(self._clean_obs, self.dones[t + 1], obs_out=seen)
+                else:
+                    sm.step(self._clean_obs, self.dones[t + 1], term_obs=term, obs_out=seen,
+                            term_out=self._term_seen)
+                    term = self._term_seen
             if vn is not None:
                 # VecNormalize.step_wait: raw scratch -> the rollout buffers
                 # (the terminal obs of done envs normalised for V(term))
@@ -543,7 +594,8 @@ class PPOTrainer:
             return (self.env.seed_value, c.seed, self.rank, c.num_envs, c.n_steps) + \
                 tuple(x for o in reversed(self.env.option_state()) for x in o) + \
                 (() if self.vecnorm is None else
-                 (v.flags(), v.gamma, v.clip_obs, v.clip_reward, v.epsilon))
+                 (v.flags(), v.gamma, v.clip_obs, v.clip_reward, v.epsilon)) + \
+                (() if self.sensor is None else self.sensor.key())
         o, kl = self.opt, self._kl
         # "linear" and "adaptive": the rate is device data (the Adam table,
         # the control block), so the key carries the mode, not the value
@@ -871,6 +923,8 @@ class PPOTrainer:
         T = self.cfg.n_steps
         # (last_obs is what the policy saw: normalised when the option is on)
         extra = {} if self.vecnorm is None else {"vecnorm": self.vecnorm.state_dict()}
+        if self.sensor is not None:
+            extra["sensor"] = self.sensor.state_dict()
         if self.cfg.kl_control_on():
             c = self.cfg
             extra["kl_control"] = {"target_kl": c.target_kl, "lr_schedule": c.lr_schedule,
@@ -915,6 +969,16 @@ class PPOTrainer:
                     self._enable_vecnorm(vs["norm_obs"], vs["norm_reward"], vs["clip_obs"],
                                          vs["clip_reward"], vs["epsilon"])
                 self.vecnorm.load_state_dict(vs)
+                self._rgraph = None
+            if "sensor" in sd:
+                # likewise a checkpoint with a sensor model: its settings, its
+                # per-env state and its ring
+                c = sd["config"]
+                want = K.check_sensor(c["obs_noise"], c["obs_bias"], tuple(c["obs_delay"]))
+                if self.sensor is None or want != (self.cfg.obs_noise, self.cfg.obs_bias,
+                                                   self.cfg.obs_delay):
+                    self._enable_sensor(*want)
+                self.sensor.load_state_dict(sd["sensor"])
                 self._rgraph = None
             if "kl_control" in sd:
                 # likewise: the checkpoint's settings, and the rate an

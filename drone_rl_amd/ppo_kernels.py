@@ -804,3 +804,197 @@ class VecNormalize:
         import numpy as np
         with np.load(path) as z:
             self.load_npz_dict(z)
+
+
+# ---------------------------------------------------------------- SensorModel
+SENSOR_GROUPS = ("pos", "vel", "att", "rate")
+# per variant: the columns of each group (each with draws of its own), and
+# (first mirror column, first source column, count): columns that show their
+# source's error with the opposite sign (target - p next to p).  Columns in
+# neither stay clean.  DESIGN.md section 23
+SENSOR_COLUMNS = {
+    "gym": ({"pos": range(0, 3), "vel": range(3, 6), "att": range(6, 9), "rate": range(9, 12)},
+            (12, 0, 3)),
+    "vectorized": ({"pos": range(0, 3), "vel": range(3, 6), "att": range(6, 9),
+                    "rate": range(9, 12)}, None),
+    "moving": ({"pos": range(0, 3), "vel": range(3, 6), "att": range(6, 9),
+                "rate": range(9, 12)}, (12, 0, 3)),
+    "smooth": ({"pos": range(0, 3), "vel": range(3, 6), "att": range(6, 9),
+                "rate": range(9, 12)}, (12, 0, 3)),
+    # the attitude is the quaternion's four components, not renormalised
+    "rk4": ({"pos": range(0, 3), "vel": range(3, 6), "att": range(6, 10),
+             "rate": range(10, 13)}, (13, 0, 3)),
+    # the other drone's relative position and velocity: estimates of their own
+    "tag": ({"pos": (0, 1, 2, 12, 13, 14), "vel": (3, 4, 5, 15, 16, 17), "att": range(6, 9),
+             "rate": range(9, 12)}, None),
+}
+
+
+def _pair(v, what):
+    try:
+        lo, hi = v
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} takes two values (lo, hi), got {v!r}") from None
+    return lo, hi
+
+
+def check_sensor(noise=(0, 0, 0, 0), bias=(0, 0, 0, 0), delay=(0, 0), max_steps=None):
+    """The value rules of the sensor model's settings,
+    raised as ValueError on the host: four noise stds and four bias
+    half-widths (pos, vel, att, rate), each finite and >= 0 in f32; integers
+    0 <= lo <= hi <= 15; a step limit below 2^24 where given.  Returns
+    (noise4, bias4, (lo, hi)) as floats / ints."""
+    import math
+    import numpy as np
+    out = []
+    for name, v in (("obs_noise", noise), ("obs_bias", bias)):
+        try:
+            v = tuple(v)
+        except TypeError:
+            raise ValueError(f"{name} takes four values (pos, vel, att, rate), got {v!r}") from None
+        if len(v) != 4:
+            raise ValueError(f"{name} takes four values (pos, vel, att, rate), got {v!r}")
+        for x in v:
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) \
+                    or x < 0 or x > float(np.finfo(np.float32).max):
+                raise ValueError(f"{name} values must be >= 0 and finite, got {x!r}")
+        out.append(tuple(float(x) for x in v))
+    lo, hi = _pair(delay, "obs_delay")
+    for x in (lo, hi):
+        if isinstance(x, bool) or not isinstance(x, int):
+            raise ValueError(f"obs_delay takes integers, got {x!r}")
+    if not 0 <= lo <= hi <= _lib.DR_SENSOR_MAX_DELAY:
+        raise ValueError(f"obs_delay needs 0 <= lo <= hi <= {_lib.DR_SENSOR_MAX_DELAY}, "
+                         f"got {(lo, hi)!r}")
+    if max_steps is not None and int(max_steps) >= 1 << 24:
+        raise ValueError("the sensor model needs max_steps below 2^24")
+    return out[0], out[1], (int(lo), int(hi))
+
+
+def sensor_neutral(noise, bias, delay) -> bool:
+    """True when the three settings leave the observation as it is."""
+    return not any(noise) and not any(bias) and tuple(delay) == (0, 0)
+
+
+def sensor_columns(variant: str, noise4, bias4):
+    """The per-column (sigma, beta, mirror) lists of a variant from the four
+    group values (SENSOR_COLUMNS)."""
+    from .env import OBS_DIM
+    if variant not in SENSOR_COLUMNS:
+        raise ValueError(f"unknown variant {variant!r}")
+    noise4, bias4, _ = check_sensor(noise4, bias4)
+    groups, mirror = SENSOR_COLUMNS[variant]
+    od = OBS_DIM[variant]
+    sigma, beta, mir = [0.0] * od, [0.0] * od, [-1] * od
+    for g, s, b in zip(SENSOR_GROUPS, noise4, bias4):
+        for c in groups[g]:
+            sigma[c], beta[c] = s, b
+    if mirror is not None:
+        first, src, count = mirror
+        for k in range(count):
+            mir[first + k] = src + k
+    return sigma, beta, mir
+
+
+class SensorModel:
+    """Observation noise, bias and latency on device tensors (dr_sensor_*,
+    DESIGN.md section 23): obs (n, obs_dim) f32 of the env in, what the policy
+    sees out, one launch per reset / step and no host round trip, so a
+    captured rollout can hold it.
+
+    `columns` = (sigma, beta, mirror), each obs_dim long (sensor_columns);
+    `delay` = (lo, hi): each episode's delay is drawn from [lo, hi] steps.
+    State: `state` int32 (3, n) = ep, s, d per env; `bias` f32 (n, obs_dim);
+    `ring` f32 (hi + 1, n, obs_dim), the clean observations."""
+
+    def __init__(self, n: int, obs_dim: int, device, columns=None, delay=(0, 0), seed: int = 0,
+                 env_id_offset: int = 0):
+        if n < 1 or not 1 <= obs_dim <= _lib.DR_SENSOR_MAX_DIM:
+            raise ValueError("SensorModel needs n >= 1 and 1 <= obs_dim <= 24")
+        self.n, self.obs_dim, self.device = int(n), int(obs_dim), torch.device(device)
+        if columns is None:
+            columns = ([0.0] * obs_dim, [0.0] * obs_dim, [-1] * obs_dim)
+        sigma, beta, mirror = (list(v) for v in columns)
+        if not len(sigma) == len(beta) == len(mirror) == self.obs_dim:
+            raise ValueError("SensorModel: columns must hold obs_dim values each")
+        _, _, (lo, hi) = check_sensor(delay=delay)
+        self.sigma, self.beta = [float(x) for x in sigma], [float(x) for x in beta]
+        self.mirror = [int(x) for x in mirror]
+        self.delay = (lo, hi)
+        self.seed, self.env_id_offset = int(seed), int(env_id_offset)
+        c = self.cfg = _lib.dr_sensor_config(delay_lo=lo, delay_hi=hi,
+                                             seed=self.seed & (2**64 - 1),
+                                             env_id_offset=self.env_id_offset)
+        for k in range(self.obs_dim):
+            c.sigma[k], c.beta[k], c.mirror[k] = self.sigma[k], self.beta[k], self.mirror[k]
+        dev = self.device
+        self.state = torch.zeros(3, self.n, dtype=torch.int32, device=dev)
+        self.bias = torch.zeros(self.n, self.obs_dim, dtype=torch.float32, device=dev)
+        self.ring = torch.zeros(hi + 1, self.n, self.obs_dim, dtype=torch.float32, device=dev)
+
+    def flags(self) -> int:
+        """1: some column has noise, 2: some has a bias, 4: a delay can occur."""
+        return (1 if any(self.sigma) else 0) | (2 if any(self.beta) else 0) | \
+            (4 if self.delay[1] else 0)
+
+    def key(self) -> tuple:
+        """Every value a captured launch holds as a kernel argument."""
+        return (self.flags(), tuple(self.sigma), tuple(self.beta), tuple(self.mirror),
+                self.delay, self.seed, self.env_id_offset)
+
+    def _rows(self, t, what):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), \
+            f"{what}: expected a contiguous f32 device tensor"
+        assert t.shape == (self.n, self.obs_dim), f"{what}: expected (n, obs_dim)"
+        return t
+
+    def reset(self, obs, out=None):
+        """Every env starts episode 0 on its reset observation; returns what
+        the policy sees of it."""
+        self._rows(obs, "obs")
+        o = torch.empty_like(obs) if out is None else self._rows(out, "out")
+        check(_lib.lib().dr_sensor_reset(ctypes.byref(self.cfg), self.n, self.obs_dim, ptr(obs),
+                                         ptr(self.state), ptr(self.bias), ptr(self.ring), ptr(o),
+                                         _s(obs)))
+        return o
+
+    def step(self, obs, dones, term_obs=None, obs_out=None, term_out=None):
+        """One env step: obs (n, obs_dim) f32 (of done envs the new episode's
+        first observation), dones (n,) u8, term_obs (n, obs_dim) f32 whose
+        rows of done envs hold the terminal observations.  Returns obs_out or,
+        with term_obs, (obs_out, term_out); rows of term_out of envs that are
+        not done are left as they were."""
+        self._rows(obs, "obs")
+        assert dones.dtype == torch.uint8 and dones.is_contiguous() and dones.shape == (self.n,)
+        o = torch.empty_like(obs) if obs_out is None else self._rows(obs_out, "obs_out")
+        if term_obs is None:
+            assert term_out is None, "term_out needs term_obs"
+            to = None
+        else:
+            self._rows(term_obs, "term_obs")
+            to = torch.empty_like(term_obs) if term_out is None else self._rows(term_out,
+                                                                                "term_out")
+        check(_lib.lib().dr_sensor_step(ctypes.byref(self.cfg), self.n, self.obs_dim, ptr(obs),
+                                        ptr(dones), ptr(term_obs), ptr(self.state),
+                                        ptr(self.bias), ptr(self.ring), ptr(o), ptr(to), _s(obs)))
+        return o if term_obs is None else (o, to)
+
+    # ------------------------------------------------------------ checkpoint
+    def state_dict(self):
+        return {"sigma": list(self.sigma), "beta": list(self.beta), "mirror": list(self.mirror),
+                "delay": list(self.delay), "seed": self.seed,
+                "env_id_offset": self.env_id_offset, "state": self.state.cpu().clone(),
+                "bias": self.bias.cpu().clone(), "ring": self.ring.cpu().clone()}
+
+    def load_state_dict(self, sd):
+        """The per-env state and the ring of a checkpoint with the same
+        settings and shapes (the settings are the constructor's)."""
+        mine = (self.sigma, self.beta, self.mirror, list(self.delay))
+        theirs = ([float(x) for x in sd["sigma"]], [float(x) for x in sd["beta"]],
+                  [int(x) for x in sd["mirror"]], [int(x) for x in sd["delay"]])
+        if mine != theirs:
+            raise ValueError("SensorModel: the checkpoint's settings differ")
+        for k in ("state", "bias", "ring"):
+            if tuple(sd[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError(f"SensorModel: the checkpoint's {k} has another shape")
+            getattr(self, k).copy_(sd[k].to(self.device))

@@ -47,6 +47,7 @@ from .policy import ActorCritic, _sb3_name
 
 SB3_VERSION = "2.3.2"
 VECNORM_MEMBER = "dronerl_vecnormalize.npz"
+SENSOR_MEMBER = "dronerl_sensor.npz"
 
 # ----------------------------------------------------------------- naming
 
@@ -251,6 +252,15 @@ def save(trainer, path):
             buf = io.BytesIO()
             np.savez(buf, **trainer.vecnorm.npz_dict())
             z.writestr(VECNORM_MEMBER, buf.getvalue())
+        if getattr(trainer, "sensor", None) is not None:
+            # the sensor model's settings (its per-env state is not kept: a
+            # load resets every env, and the sensor with them)
+            c = trainer.cfg
+            buf = io.BytesIO()
+            np.savez(buf, obs_noise=np.asarray(c.obs_noise, np.float64),
+                     obs_bias=np.asarray(c.obs_bias, np.float64),
+                     obs_delay=np.asarray(c.obs_delay, np.int64))
+            z.writestr(SENSOR_MEMBER, buf.getvalue())
 
 
 # ---------------------------------------------------------------- reading
@@ -275,6 +285,9 @@ def read(path):
         if VECNORM_MEMBER in names:
             with np.load(io.BytesIO(z.read(VECNORM_MEMBER))) as f:
                 out["vecnorm"] = {k: f[k] for k in f.files}
+        if SENSOR_MEMBER in names:
+            with np.load(io.BytesIO(z.read(SENSOR_MEMBER))) as f:
+                out["sensor"] = {k: f[k] for k in f.files}
     if out["policy"] is None:
         raise ValueError(f"{path}: no policy.pth member (not an SB3 checkpoint)")
     return out
@@ -332,6 +345,12 @@ def load_into(trainer, path, load_env_state=True):
                                     bool(vn.get("norm_reward", True)), float(vn["clip_obs"]),
                                     float(vn["clip_reward"]), float(vn["epsilon"]))
         trainer.vecnorm.load_npz_dict(vn)
+    sm = ck.get("sensor")
+    if sm is not None and hasattr(trainer, "_enable_sensor"):
+        # likewise a checkpoint trained behind a sensor model: its settings
+        trainer._enable_sensor(tuple(float(x) for x in sm["obs_noise"]),
+                               tuple(float(x) for x in sm["obs_bias"]),
+                               tuple(int(x) for x in sm["obs_delay"]))
     tkl = ck["data"].get("target_kl")
     if tkl is not None and hasattr(trainer, "_enable_kl") and trainer.cfg.target_kl is None:
         # likewise a checkpoint with an early stop: the trainer takes it (the

@@ -49,6 +49,20 @@ def resume_path(path: str, rank: int, world: int) -> str | None:
     return None
 
 
+def _floats4(text: str) -> tuple:
+    v = tuple(float(x) for x in text.split(","))
+    if len(v) != 4:
+        raise argparse.ArgumentTypeError("expected four comma-separated values P,V,A,R")
+    return v
+
+
+def _ints2(text: str) -> tuple:
+    v = tuple(int(x) for x in text.split(","))
+    if len(v) != 2:
+        raise argparse.ArgumentTypeError("expected two comma-separated integers LO,HI")
+    return v
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
@@ -115,6 +129,14 @@ def build_parser():
                     help="lower bound of the adaptive learning rate")
     ap.add_argument("--lr-max", type=float, default=1e-2,
                     help="upper bound of the adaptive learning rate")
+    ap.add_argument("--obs-noise", type=_floats4, default=(0.0,) * 4, metavar="P,V,A,R",
+                    help="sensor model: noise std of the position, velocity, attitude and "
+                         "body-rate observations")
+    ap.add_argument("--obs-bias", type=_floats4, default=(0.0,) * 4, metavar="P,V,A,R",
+                    help="sensor model: half-width of the per-episode bias of the same four")
+    ap.add_argument("--obs-delay", type=_ints2, default=(0, 0), metavar="LO,HI",
+                    help="sensor model: each episode's observation latency is drawn from "
+                         "LO..HI steps (HI <= 15)")
     return ap
 
 
@@ -128,6 +150,7 @@ def config_from_args(a) -> PPOConfig:
                   clip_obs=a.clip_obs, clip_reward=a.clip_reward,
                   target_kl=a.target_kl, lr_schedule=a.lr_schedule, desired_kl=a.desired_kl,
                   lr_min=a.lr_min, lr_max=a.lr_max,
+                  obs_noise=a.obs_noise, obs_bias=a.obs_bias, obs_delay=a.obs_delay,
                   eps_schedule=tuple((int(u), float(e)) for u, e in
                                      (kv.split(":") for kv in a.eps_schedule.split(",") if kv)))
     if a.sb3_defaults:

@@ -950,6 +950,72 @@ int dr_vecnorm_apply(int64_t m, int64_t obs_dim, const float *obs, const double 
 int dr_vecnorm_unapply(int64_t m, int64_t obs_dim, const float *obs_norm, const double *obs_rms,
                        double epsilon, float *obs_out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * SensorModel: what the policy sees of the env's clean
+ * observation -- per-column noise, a per-episode bias and a per-episode
+ * latency -- as a wrapper with its state on the device, so that it can sit
+ * inside a captured rollout, around any variant and any env option.  The obs
+ * width is unchanged.  All buffers are device memory, owned by the caller and
+ * separate (there is no packed state blob, so a checkpoint and a test can read
+ * each word):
+ *     state  int32[3][n]      ep (u32 bits), s, d per env
+ *     bias   float[n][obs_dim]
+ *     ring   float[delay_hi + 1][n][obs_dim]   clean observations
+ * ep counts the episodes the wrapper has started for the env, s the
+ * deliveries since the episode began, d is the episode's delay in steps.  The
+ * wrapper reads none of the env's counters.
+ *
+ * Episode start (every env at dr_sensor_reset; in dr_sensor_step an env whose
+ * done is set, obs being the new episode's first observation): ep <- 0 at a
+ * reset, ep + 1 after a done; s <- 0; with the Philox blocks of counter
+ * (ep, gid_lo, gid_hi, word) under the key `seed`, gid = env_id_offset + env,
+ *     d      <- delay_lo + ((uint64(w0 of word 0x53000000) * (delay_hi -
+ *               delay_lo + 1)) >> 32)
+ *     bias_c <- beta_c * pm1(word c % 4 of block 0x53000000 | (1 + c / 4)),
+ * pm1(w) = f32(2 (w 2^-32) - 1); all delay_hi + 1 ring slots <- obs.
+ * Delivery at count s: x = ring[(s - d) mod (delay_hi + 1)];
+ *     e_c = bias_c + sigma'_c * pm1(word c % 4 of block
+ *           ((0x60 + c / 4) << 24) | (s & 0xffffff)),
+ * sigma'_c = f32(f64(sigma_c) * sqrt(3)); out_c = x_c + e_c, or x_c - e_m for
+ * a column with mirror[c] = m >= 0; a column whose sigma and beta (its
+ * source's, for a mirror) are both 0 is delivered unchanged, x_c.  Every f32
+ * operation rounds once, none is contracted.  s enters the counter modulo
+ * 2^24: episodes must be shorter than that.
+ * dr_sensor_step per env: not done -- s <- s + 1, ring[s mod L] <- obs,
+ * deliver; done -- with the terminal pair, terminal_out[env] is the delivery
+ * the old episode would have made at s + 1 with terminal_obs[env] as that
+ * step's clean row (rows of envs that are not done are left untouched); then
+ * the episode start on obs[env] and its delivery at count 0.  obs_out may be
+ * obs.  One launch each, no atomics, no host sync: results are bitwise equal
+ * from run to run and under graph replay.
+ *
+ * DR_ERR_INVALID, before any HIP call, with a dr_last_error(NULL) message
+ * naming the argument: a null config, n < 1, obs_dim outside [1, 24], a
+ * negative or non-finite sigma or beta, a mirror index outside [-1, c), a
+ * delay pair that is not 0 <= delay_lo <= delay_hi <= 15, a missing buffer,
+ * terminal_obs without terminal_out or the reverse.
+ * These additions break no caller: DR_ABI_VERSION stays 16.
+ * ------------------------------------------------------------------------- */
+#define DR_SENSOR_MAX_DIM 24
+#define DR_SENSOR_MAX_DELAY 15
+
+typedef struct dr_sensor_config {
+    int32_t delay_lo, delay_hi;          /* the delay is drawn from [lo, hi]     */
+    uint64_t seed;                       /* Philox key                           */
+    int64_t env_id_offset;               /* global id of env 0                   */
+    float sigma[DR_SENSOR_MAX_DIM];      /* noise std per column                 */
+    float beta[DR_SENSOR_MAX_DIM];       /* bias half-width per column           */
+    int32_t mirror[DR_SENSOR_MAX_DIM];   /* -1, or the column whose error this
+                                            one shows with the opposite sign     */
+} dr_sensor_config;
+
+int dr_sensor_reset(const dr_sensor_config *cfg, int64_t n, int64_t obs_dim, const float *obs,
+                    int32_t *state, float *bias, float *ring, float *obs_out, void *stream);
+
+int dr_sensor_step(const dr_sensor_config *cfg, int64_t n, int64_t obs_dim, const float *obs,
+                   const uint8_t *dones, const float *terminal_obs, int32_t *state, float *bias,
+                   float *ring, float *obs_out, float *terminal_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

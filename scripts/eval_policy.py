@@ -49,11 +49,21 @@ is evaluated through them, frozen: the policy sees normalize_obs(obs) of the
 raw env's observations, and every reported reward is the env's raw one.
 --no-normalize feeds the raw observations instead.
 
+Any checkpoint is put behind a sensor model with
+--obs-noise P,V,A,R / --obs-bias P,V,A,R / --obs-delay LO,HI: the policy sees
+the env's observation with that noise, per-episode bias and latency (ahead of
+the frozen VecNormalize statistics, if any); every reported figure is of the
+true state.  A flag not given takes the checkpoint's value (neutral for
+checkpoints from before the option), so `--obs-noise 0,0,0,0 --obs-bias
+0,0,0,0 --obs-delay 0,0` flies a sensor-trained policy on exact state.
+
   python scripts/eval_policy.py CKPT --eps 1.0 [--envs 65536 --steps 400]
                                 [--drag 0.5 --wind-speed 2 --gust-sigma 0.5 --gust-rate 0.1]
                                 [--reach-radius 0.25 --reach-bonus 1]
                                 [--mass-spread 0.3 --inertia-spread 0.3 --motor-spread 0.1]
                                 [--fixed-airframe 1.3,1,0.9,1,1,1]
+                                [--obs-noise 0.02,0.05,0.02,0.1 --obs-bias 0.02,0,0.01,0
+                                 --obs-delay 0,2]
 """
 import argparse
 import json
@@ -113,10 +123,40 @@ def frozen_normaliser(sd, envs, obs_dim, dev, normalize=True):
     return lambda obs: vn.normalize_obs(obs, out=buf)
 
 
+NO_SENSOR = ((0.0,) * 4, (0.0,) * 4, (0, 0))
+
+
+def sensor_of(cfg, args):
+    """(noise4, bias4, (lo, hi)): per setting the command line's, else the
+    checkpoint's (neutral for checkpoints from before the option), checked."""
+    from drone_rl_amd import ppo_kernels as K
+    from drone_rl_amd.train import _floats4, _ints2
+    given = (None if args.obs_noise is None else _floats4(args.obs_noise),
+             None if args.obs_bias is None else _floats4(args.obs_bias),
+             None if args.obs_delay is None else _ints2(args.obs_delay))
+    return K.check_sensor(*(tuple(cfg.get(k, d)) if g is None else g
+                            for g, k, d in zip(given, ("obs_noise", "obs_bias", "obs_delay"),
+                                               NO_SENSOR)))
+
+
+def sensor_front(variant, sensor, envs, obs_dim, dev, seed):
+    """(reset, step): the env's clean observation -> what the policy sees of
+    it (both the identity for neutral settings)."""
+    from drone_rl_amd import ppo_kernels as K
+    noise, bias, delay = sensor
+    if K.sensor_neutral(noise, bias, delay):
+        return (lambda obs: obs), (lambda obs, done: obs)
+    sm = K.SensorModel(envs, obs_dim, dev, columns=K.sensor_columns(variant, noise, bias),
+                       delay=delay, seed=seed, env_id_offset=1 << 40)
+    buf = torch.empty(envs, obs_dim, dtype=torch.float32, device=dev)
+    return (lambda obs: sm.reset(obs, out=buf)), \
+        (lambda obs, done: sm.step(obs, done.contiguous(), obs_out=buf))
+
+
 @torch.no_grad()
 def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0.0),
              course=(None, None), airframe=(0.0, 0.0, 0.0), fixed_airframe=None,
-             normalize=True):
+             normalize=True, sensor=NO_SENSOR):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -142,6 +182,8 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
     norm = frozen_normaliser(sd, envs, OBS_DIM[variant], dev, normalize)
+    see_reset, see_step = sensor_front(variant, sensor, envs, OBS_DIM[variant], dev, seed)
+    seen = see_reset(obs)
     g = torch.Generator(device=dev).manual_seed(seed)
     std = pol.log_std.exp()
     ret_sum = len_sum = n_done = n_crash = 0.0
@@ -152,7 +194,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
     ep_ret = torch.empty(envs, device=dev)
     ep_len = torch.empty(envs, dtype=torch.int32, device=dev)
     for _ in range(steps):
-        mean, _ = infer(norm(obs))
+        mean, _ = infer(norm(seen))
         a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
                                                                  device=dev)
         env.ep_ret, env.ep_len = ep_ret, ep_len
@@ -164,6 +206,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
             env.set("airframe", fixed)
         o, r, d = env.step(cmd)
         obs = o.clone()
+        seen = see_step(obs, d)
         db = d.bool()
         if not smooth:
             force = torch.where(db[:, None], torch.full_like(cmd, HOVER), cmd)
@@ -188,7 +231,7 @@ def evaluate(ckpt, eps, envs, steps, seed, deterministic, wind=(0.0, 0.0, 0.0, 0
 
 
 @torch.no_grad()
-def evaluate_tag(ckpt, envs, steps, seed, deterministic, normalize=True):
+def evaluate_tag(ckpt, envs, steps, seed, deterministic, normalize=True, sensor=NO_SENSOR):
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     cfg = sd["config"]
     dev = torch.device("cuda", 0)
@@ -200,6 +243,8 @@ def evaluate_tag(ckpt, envs, steps, seed, deterministic, normalize=True):
     obs = env.reset().clone()
     infer = PolicyInference(pol, envs)
     norm = frozen_normaliser(sd, envs, OBS_DIM["tag"], dev, normalize)
+    see_reset, see_step = sensor_front("tag", sensor, envs, OBS_DIM["tag"], dev, seed)
+    seen = see_reset(obs)
     g = torch.Generator(device=dev).manual_seed(seed)
     std = pol.log_std.exp()
     ep_ret = torch.empty(envs, device=dev)
@@ -210,12 +255,13 @@ def evaluate_tag(ckpt, envs, steps, seed, deterministic, normalize=True):
     crashed = [0.0, 0.0]
     len_sum = tagged = dist = 0.0
     for _ in range(steps):
-        mean, _ = infer(norm(obs))
+        mean, _ = infer(norm(seen))
         a = mean if deterministic else mean + std * torch.randn(mean.shape, generator=g,
                                                                  device=dev)
         env.ep_ret, env.ep_len = ep_ret, ep_len
         o, r, d = env.step(a.clamp(0.0, MOTOR_MAX).contiguous())
         obs = o.clone()
+        seen = see_step(obs, d)
         db = d.bool()
         # the state the step ended in: the terminal obs where the pair was reset
         end = torch.where(db[:, None], env.term_obs, o)
@@ -254,6 +300,13 @@ def main():
     ap.add_argument("--no-normalize", action="store_true",
                     help="checkpoints with VecNormalize statistics: feed the policy the raw "
                          "observations instead of the normalised ones")
+    ap.add_argument("--obs-noise", default=None, metavar="P,V,A,R",
+                    help="sensor model: noise std of the position, velocity, attitude and "
+                         "body-rate observations (default: the checkpoint's)")
+    ap.add_argument("--obs-bias", default=None, metavar="P,V,A,R",
+                    help="sensor model: half-width of the per-episode bias of the same four")
+    ap.add_argument("--obs-delay", default=None, metavar="LO,HI",
+                    help="sensor model: per-episode observation latency drawn from LO..HI steps")
     a = ap.parse_args()
     out = {"ckpt": os.path.basename(a.ckpt), "eps": a.eps, "envs": a.envs, "steps": a.steps}
     sd = torch.load(a.ckpt, map_location="cpu", weights_only=True)
@@ -261,6 +314,9 @@ def main():
     if "vecnorm" in sd:
         out["normalized"] = not a.no_normalize
     out["variant"] = cfg.get("variant", "gym")
+    sensor = sensor_of(cfg, a)
+    if sensor != NO_SENSOR:
+        out.update(zip(("obs_noise", "obs_bias", "obs_delay"), sensor))
     if out["variant"] == "smooth":
         out["motor_alpha"] = cfg.get("motor_alpha", 1.0)
         out["rate_penalty"] = cfg.get("rate_penalty", 0.0)
@@ -295,10 +351,10 @@ def main():
             out["fixed_airframe"] = fixed
     for det in (True, False):
         out["deterministic" if det else "sampled"] = (
-            evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det, not a.no_normalize)
+            evaluate_tag(a.ckpt, a.envs, a.steps, a.seed, det, not a.no_normalize, sensor)
             if out["variant"] == "tag"
             else evaluate(a.ckpt, a.eps, a.envs, a.steps, a.seed, det, wind, course, airframe,
-                          fixed, not a.no_normalize))
+                          fixed, not a.no_normalize, sensor))
     print(json.dumps(out), flush=True)
 
 
