@@ -39,6 +39,8 @@ DR_VECNORM_REWARD = 2
 DR_VECNORM_TRAINING = 4
 DR_SENSOR_MAX_DIM = 24
 DR_SENSOR_MAX_DELAY = 15
+DR_MPPI_MAX_SAMPLES = 1024
+DR_MPPI_MAX_HORIZON = 32
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
@@ -82,6 +84,13 @@ class dr_sensor_config(ctypes.Structure):
     _fields_ = [("delay_lo", c_int32), ("delay_hi", c_int32), ("seed", c_uint64),
                 ("env_id_offset", c_int64), ("sigma", c_float * DR_SENSOR_MAX_DIM),
                 ("beta", c_float * DR_SENSOR_MAX_DIM), ("mirror", c_int32 * DR_SENSOR_MAX_DIM)]
+
+
+class dr_mppi_config(ctypes.Structure):
+    """include/dronerl.h dr_mppi_config (MPPIPlanner)."""
+    _fields_ = [("samples", c_int32), ("horizon", c_int32), ("sigma", c_double),
+                ("temperature", c_double), ("gamma", c_double), ("crash_cost", c_double),
+                ("terminal_weight", c_double), ("seed", c_uint64), ("env_id_offset", c_int64)]
 
 
 class DroneRLError(RuntimeError):
@@ -196,6 +205,8 @@ SIGNATURES = {
     "dr_vecnorm_unapply": (c_int, [c_int64, c_int64, _P, _P, c_double, _P, _P]),
     "dr_sensor_reset": (c_int, [POINTER(dr_sensor_config), c_int64, c_int64] + [_P] * 6),
     "dr_sensor_step": (c_int, [POINTER(dr_sensor_config), c_int64, c_int64] + [_P] * 9),
+    "dr_mppi_reset": (c_int, [POINTER(dr_mppi_config), c_int64] + [_P] * 3),
+    "dr_mppi_step": (c_int, [POINTER(dr_mppi_config), c_int64] + [_P] * 7),
 }
 
 _lib = None

@@ -104,7 +104,8 @@ enum : uint32_t {
     TAG_PERM = 0x50000000u,     // minibatch permutation keys
     TAG_GUST = 0x47000000u,     // wind gust noise, the env's step counter in low bits
     TAG_WAYPOINT = 0x57000000u, // waypoint courses, the waypoint's index in low bits
-    TAG_AIRFRAME = 0x46000000u  // airframe randomisation, block index in low bits
+    TAG_AIRFRAME = 0x46000000u, // airframe randomisation, block index in low bits
+    TAG_PLAN = 0x4D000000u      // MPPI action noise, sample * horizon + step in low bits
 };
 
 // The network's tanh (every kernel that applies it calls tanh_fast / tanh4,

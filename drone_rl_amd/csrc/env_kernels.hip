@@ -3797,3 +3797,7 @@ const char *dr_last_error(const dr_handle *h) {
 }
 
 }  // extern "C"
+
+// MPPIPlanner (dr_mppi_*): its own file, this translation unit (the model it
+// plans on is physics_step above).
+#include "planner.hip"

@@ -1016,6 +1016,78 @@ int dr_sensor_step(const dr_sensor_config *cfg, int64_t n, int64_t obs_dim, cons
                    const uint8_t *dones, const float *terminal_obs, int32_t *state, float *bias,
                    float *ring, float *obs_out, float *terminal_out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * MPPIPlanner: model-predictive path integral control
+ * on the gym env's own step.  For every env it flies `samples` perturbed
+ * action sequences `horizon` steps ahead from the env's 15-float observation,
+ * weights them by exponentiated return and outputs the first action of the
+ * weighted mean; the mean, shifted by one step, warm-starts the next call.
+ * The planner's model is the nominal airframe in still air; it reads no env
+ * handle, only the observation a policy would see.  All buffers are device
+ * memory, owned by the caller and separate:
+ *     nominal  float[n][horizon][4]   the warm start U
+ *     calls    uint32[n]              plan steps since the reset
+ * dr_mppi_reset: every nominal entry <- f32(9.81 / 4) (hover), calls <- 0.
+ * dr_mppi_step for env e (gid = env_id_offset + e), with S = samples,
+ * H = horizon, M = f32(3 * 9.81 / 4), clip(x) = x < 0 ? 0 : x > M ? M : x:
+ *  0. where dones is given and dones[e] is set, obs[e] opens a new episode:
+ *     U <- hover first.
+ *  1. Start state in f64: p, v, euler, omega = (double)obs[0..11]; target_k =
+ *     (double)obs[k] + (double)obs[12 + k].
+ *  2. Sample s at step h: a_k = clip(U[h][k]) for s = 0, else
+ *     clip(U[h][k] + sigma' * pm1(w_k)) in f32, one rounding per operation,
+ *     w the Philox4x32-10 block of counter (calls, gid_lo, gid_hi, 0x4D000000 |
+ *     (s * H + h)) under the key `seed`, pm1(w) = f32(2 (w 2^-32) - 1),
+ *     sigma' = f32(sigma * sqrt(3)).
+ *  3. The sample steps the gym env's f64 step (dt = 0.02, no reset inside the
+ *     horizon).  While it has not crashed before step h,
+ *         J <- J + disc[h] * ((double)(float)r - (crash ? crash_cost : 0)),
+ *     r and crash that step's reward and crash flag, disc[0] = 1, disc[h] =
+ *     disc[h - 1] * gamma.  A sample that never crashed ends with J <- J -
+ *     terminal_weight * d, d = sqrt((dx dx + dy dy) + dz dz) from the final
+ *     position to the target.
+ *  4. Jmax = the maximum J over the samples whose J is not NaN; w_s =
+ *     exp((J_s - Jmax) / temperature), 0 where J_s is NaN; W = sum of w_s, all
+ *     in f64 and in a fixed order.  Where Jmax is not finite (no sample has a
+ *     finite return: a NaN observation) the nominal is left as it is (as step
+ *     0 left it) and actions_out[e] = clip(U[0]); calls still counts on.
+ *  5. U_new[h][k] = f32(sum_s w_s * (double)a_s[h][k] / W).
+ *  6. actions_out[e] = U_new[0]; nominal[h] <- U_new[h + 1] for h < H - 1,
+ *     nominal[H - 1] <- U_new[H - 1]; calls <- calls + 1.
+ *  7. costs_out, where given: double[n][S], every J_s.
+ * One launch each, asynchronous on `stream`, no atomics, no host sync: results
+ * are bitwise equal from run to run and under graph replay.  The config is
+ * copied into the kernel's arguments at the call.
+ *
+ * DR_ERR_INVALID, before any HIP call, with a dr_last_error(NULL) message
+ * naming the argument: a null config, n < 1, samples not one of 64, 128, 256,
+ * 512, 1024, horizon outside [1, 32], sigma, crash_cost or terminal_weight
+ * negative or not finite, temperature not > 0 and finite, gamma outside
+ * (0, 1], a missing nominal, calls, obs or actions_out.
+ * These additions break no caller: DR_ABI_VERSION stays 16.
+ * ------------------------------------------------------------------------- */
+#define DR_MPPI_MAX_SAMPLES 1024
+#define DR_MPPI_MAX_HORIZON 32
+
+typedef struct dr_mppi_config {
+    int32_t samples;                     /* S: 64, 128, 256, 512 or 1024         */
+    int32_t horizon;                     /* H: 1 .. 32 steps                     */
+    double sigma;                        /* action noise std, newtons per motor  */
+    double temperature;                  /* lambda                               */
+    double gamma;                        /* discount per step                    */
+    double crash_cost;                   /* what the step that crashes pays      */
+    double terminal_weight;              /* on the final distance to the target  */
+    uint64_t seed;                       /* Philox key                           */
+    int64_t env_id_offset;               /* global id of env 0                   */
+} dr_mppi_config;
+
+int dr_mppi_reset(const dr_mppi_config *cfg, int64_t n, float *nominal, uint32_t *calls,
+                  void *stream);
+
+int dr_mppi_step(const dr_mppi_config *cfg, int64_t n, const float *obs, const uint8_t *dones,
+                 float *nominal, uint32_t *calls, float *actions_out, double *costs_out,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
