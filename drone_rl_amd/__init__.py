@@ -9,4 +9,5 @@ __version__ = "0.1.0"
 
 from .env import (DT, G, MASS, MAX_STEPS, MOTOR_MAX, DroneBatch,  # noqa: F401
                   DroneGymEnv, random_actions)
+from .grad_planner import GradPlanner  # noqa: F401
 from .planner import MPPIPlanner  # noqa: F401

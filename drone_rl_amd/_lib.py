@@ -41,6 +41,8 @@ DR_SENSOR_MAX_DIM = 24
 DR_SENSOR_MAX_DELAY = 15
 DR_MPPI_MAX_SAMPLES = 1024
 DR_MPPI_MAX_HORIZON = 32
+DR_GPLAN_MAX_HORIZON = 32
+DR_GPLAN_MAX_ITERATIONS = 64
 
 FIELDS = {"pos": 0, "vel": 1, "euler": 2, "omega": 3, "target": 4,
           "current_step": 5, "ep_num": 6, "eps": 7, "ep_return": 8,
@@ -91,6 +93,15 @@ class dr_mppi_config(ctypes.Structure):
     _fields_ = [("samples", c_int32), ("horizon", c_int32), ("sigma", c_double),
                 ("temperature", c_double), ("gamma", c_double), ("crash_cost", c_double),
                 ("terminal_weight", c_double), ("seed", c_uint64), ("env_id_offset", c_int64)]
+
+
+class dr_gplan_config(ctypes.Structure):
+    """include/dronerl.h dr_gplan_config (GradPlanner)."""
+    _fields_ = [("horizon", c_int32), ("iterations", c_int32), ("lr", c_double),
+                ("beta1", c_double), ("beta2", c_double), ("adam_eps", c_double),
+                ("w_pos", c_double), ("w_vel", c_double), ("w_att", c_double),
+                ("w_rate", c_double), ("w_effort", c_double), ("w_pos_final", c_double),
+                ("w_vel_final", c_double)]
 
 
 class DroneRLError(RuntimeError):
@@ -207,6 +218,10 @@ SIGNATURES = {
     "dr_sensor_step": (c_int, [POINTER(dr_sensor_config), c_int64, c_int64] + [_P] * 9),
     "dr_mppi_reset": (c_int, [POINTER(dr_mppi_config), c_int64] + [_P] * 3),
     "dr_mppi_step": (c_int, [POINTER(dr_mppi_config), c_int64] + [_P] * 7),
+    "dr_gplan_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "dr_gplan_reset": (c_int, [POINTER(dr_gplan_config), c_int64, _P, _P]),
+    "dr_gplan_step": (c_int, [POINTER(dr_gplan_config), c_int64] + [_P] * 4 + [c_size_t] +
+                      [_P] * 4),
 }
 
 _lib = None

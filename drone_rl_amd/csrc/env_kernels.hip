@@ -3801,3 +3801,7 @@ const char *dr_last_error(const dr_handle *h) {
 // MPPIPlanner (dr_mppi_*): its own file, this translation unit (the model it
 // plans on is physics_step above).
 #include "planner.hip"
+
+// GradPlanner (dr_gplan_*): the adjoint of physics_step and the planner on it,
+// after planner.hip, whose clip it shares.
+#include "grad_planner.hip"

@@ -1088,6 +1088,79 @@ int dr_mppi_step(const dr_mppi_config *cfg, int64_t n, const float *obs, const u
                  float *nominal, uint32_t *calls, float *actions_out, double *costs_out,
                  void *stream);
 
+/* ---------------------------------------------------------------------------
+ * GradPlanner: gradient trajectory planning by the
+ * adjoint of the gym env's own step.  For every env it takes `iterations` Adam
+ * steps on the warm-started action sequence U, each on the gradient of a
+ * quadratic tracking cost through `horizon` steps of the gym env's f64 step,
+ * and outputs the first action; the sequence, shifted by one step, warm-starts
+ * the next call.  The model is the nominal airframe in still air; it reads no
+ * env handle, only the 15-float observation a policy would see.  Device
+ * buffers, owned by the caller and separate:
+ *     nominal    float[n][horizon][4]   the warm start U
+ *     workspace  dr_gplan_workspace_bytes(n, horizon) bytes, 8-byte aligned;
+ *                scratch of one call, nothing is kept in it between calls
+ * dr_gplan_reset: every nominal entry <- f32(9.81 / 4) (hover).
+ * dr_gplan_step for env e, with H = horizon, M = f32(3 * 9.81 / 4), clip(x) =
+ * x < 0 ? 0 : x > M ? M : x, hover = (double)f32(9.81 / 4):
+ *  0. where dones is given and dones[e] is set, obs[e] opens a new episode:
+ *     U <- hover first.
+ *  1. Start state in f64: p, v, euler, omega = (double)obs[0..11]; target_k =
+ *     (double)obs[k] + (double)obs[12 + k].
+ *  2. The cost of U: H gym steps (dt = 0.02, no reset, the crash rule and the
+ *     bonus play no part) on a_h = clip(U[h]); after step h, on the new state,
+ *         c <- c + ((((w_pos |p - target|^2 + w_vel |v|^2) + w_att |euler|^2)
+ *                    + w_rate |omega|^2) + w_effort |a_h - hover|^2),
+ *     |x|^2 = (x0 x0 + x1 x1) + x2 x2, and after the last step
+ *         c <- c + (w_pos_final |p - target|^2 + w_vel_final |v|^2).
+ *  3. g = dc/dU, double[H][4], by the adjoint of the step; the f32 casts and
+ *     the clip are taken as the identity.
+ *  4. Adam, fresh at every call (m = s = 0), for it = 1 .. iterations:
+ *         m <- beta1 m + (1 - beta1) g;  s <- beta2 s + (1 - beta2) (g g);
+ *         U <- clip((float)((double)U - (lr (m / (1 - beta1^it)))
+ *                                       / (sqrt(s / (1 - beta2^it)) + adam_eps)))
+ *     with beta^it the running product, and g taken anew on the updated U.
+ *  5. Where the cost or a gradient entry of iteration 1 is not finite (a NaN
+ *     observation) the nominal is left as step 0 left it and actions_out[e] =
+ *     clip(U[0]); no other env is touched.
+ *  6. actions_out[e] = U[0]; nominal[h] <- U[h + 1] for h < H - 1,
+ *     nominal[H - 1] <- U[H - 1].
+ *  7. cost_out, where given: double[n], the cost of the incoming nominal (as
+ *     step 0 left it); grad_out, where given: double[n][H][4], its gradient.
+ * One launch each, asynchronous on `stream`, no atomics, no host sync: results
+ * are bitwise equal from run to run and under graph replay.  The config is
+ * copied into the kernel's arguments at the call.
+ *
+ * DR_ERR_INVALID, before any HIP call, with a dr_last_error(NULL) message
+ * naming the argument: a null config, n < 1, horizon outside [1, 32],
+ * iterations outside [1, 64], lr or adam_eps not > 0 and finite, beta1 or
+ * beta2 outside [0, 1), a weight negative or not finite, a missing nominal,
+ * obs, actions_out or workspace, a workspace that is not 8-byte aligned or
+ * smaller than dr_gplan_workspace_bytes(n, horizon) (which is 0 for an n or a
+ * horizon outside its range).
+ * These additions break no caller: DR_ABI_VERSION stays 16.
+ * ------------------------------------------------------------------------- */
+#define DR_GPLAN_MAX_HORIZON 32
+#define DR_GPLAN_MAX_ITERATIONS 64
+
+typedef struct dr_gplan_config {
+    int32_t horizon;                     /* H: 1 .. 32 steps                     */
+    int32_t iterations;                  /* Adam steps per call: 1 .. 64         */
+    double lr;                           /* Adam step, newtons per motor         */
+    double beta1, beta2, adam_eps;
+    double w_pos, w_vel, w_att, w_rate;  /* per step, on the new state           */
+    double w_effort;                     /* per step, on a_h - hover             */
+    double w_pos_final, w_vel_final;     /* on the state after the last step     */
+} dr_gplan_config;
+
+size_t dr_gplan_workspace_bytes(int64_t n, int32_t horizon);
+
+int dr_gplan_reset(const dr_gplan_config *cfg, int64_t n, float *nominal, void *stream);
+
+int dr_gplan_step(const dr_gplan_config *cfg, int64_t n, const float *obs, const uint8_t *dones,
+                  float *nominal, void *workspace, size_t workspace_bytes, float *actions_out,
+                  double *cost_out, double *grad_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
